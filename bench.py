@@ -8,7 +8,7 @@ GPUs), T = 128 rollout steps per iteration (16.8M env-steps per GPU), GAE, then 
 value net, Adam lr 3e-4, gamma 0.99).  A "step" is one full PPO iteration.  Synthetic data (the
 env itself generates it); random-init weights; fp32-accurate arithmetic throughout.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
   (--config picks another BASELINE.json workload — c2: 4,096 envs/GPU (configs[1]); c3: 65,536
    node-level envs x 8 clusters x 256 nodes; c5: 64 x 1,024 nodes with the Locust-fitted MMPP
    arrivals and the [2048, 2048] policy on the generic-width path; the default is c4)
@@ -20,9 +20,15 @@ env itself generates it); random-init weights; fp32-accurate arithmetic througho
    fixed at 8x the per-GPU figures (c4: 1,048,576 lanes, a 524,288-row global minibatch) and each
    of the N ranks owns 1/N of it, so one PPO iteration is the same computation at every N.)
 
-Prints ONE JSON line on rank 0.  Also measures, with HIP events on the launch stream, the average
-duration of each kernel of the SGD step (roofline of the dominant one), of the env step kernel and
-of the GAE scan, and times the CPU port (oracle/cpu_ppo.py) on the host cores as cpu_baseline.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line
+(value, ms_per_step, config, finite); roofline, cpu_baseline, allreduce and kernels are null.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step left for its caller
+(parameters, Adam moments, learner stats, the rollout and advantage buffers) as DIR/<name>.npy
+(dump_outputs).  The seeds are fixed, so two runs with the same arguments start from identical inputs.
+--full: also measures, with HIP events on the launch stream, the average duration of each kernel of
+the SGD step (roofline of the dominant one), of the env step kernel and of the GAE scan, profiles the
+gradient all-reduce (multi-rank), and times the CPU port (oracle/cpu_ppo.py) on the host cores as
+cpu_baseline; --no-kernel-timing / --no-cpu-baseline drop a leg of it.
 """
 from __future__ import annotations
 
@@ -139,8 +145,13 @@ def parse():
     ap.add_argument("--rollout", type=int, default=128)
     ap.add_argument("--minibatch", type=int, default=None, help="rows per GPU per SGD step (default: the config's)")
     ap.add_argument("--epochs", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel / roofline figures, the multi-rank "
+                         "all-reduce profile and the CPU baseline (runs of their own; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the kernel timings and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--precision", default="auto", choices=("auto", "sf16", "fp32", "f16"),
                     help="SGD-step matrix arithmetic (f16: one-product throughput mode, below fp32: a secondary line)")
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
@@ -583,6 +594,34 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
 
 
+DUMP_MAX_ELEMS = 1 << 19  # per array: 2 MB of float32, so the ~16 arrays stay far below 64 MB in all
+DUMP_SEED = 20240229
+
+
+def dump_outputs(algo, torch, out_dir):
+    """--dump-outputs: what train_step_no_sync left for its caller after the last timed step, one
+    DIR/<name>.npy per array: the flat parameters, Adam moments and last gradient, the per-SGD-step
+    learner stats and episode sums (float64), the dynamic scalars (KL coefficient, advantage mean /
+    scale) and the rollout / advantage buffers the update read (float32; integer buffers converted).
+    An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of that many of its
+    flattened elements (sorted indices from numpy's default_rng(DUMP_SEED), the same for every run
+    and build)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"params": algo.params.flat, "adam_m": algo.adam_m, "adam_v": algo.adam_v, "grad": algo.grad,
+              "stats": algo.stats, "ep_stats": algo.ep_stats, "dyn": algo.dyn}
+    arrays.update({f"rollout_{k}": v for k, v in algo.buf.items()})
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            flat = flat.reshape(t.shape)
+        a = flat.cpu().numpy()
+        np.save(out / f"{name}.npy", a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 METRIC = "env-steps/sec (node), batched rollout+policy update, 1/2/4/8 GPUs; %HBM BW"
 
 
@@ -664,10 +703,12 @@ def main():
     steps_total = algo.samples * world * args.steps
     value = steps_total / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(algo, torch, args.dump_outputs)
 
-    # multi-rank: one more (untimed) iteration with events around every gradient all-reduce
-    allreduce = algo.profile_allreduce() if algo.multi else None
-    kernels = None if args.no_kernel_timing else kernel_timing(algo, torch, args.config)
+    # --full, multi-rank: one more (untimed) iteration with events around every gradient all-reduce
+    allreduce = algo.profile_allreduce() if args.full and algo.multi else None
+    kernels = kernel_timing(algo, torch, args.config) if args.full and not args.no_kernel_timing else None
     # sanity: the policy is learning something finite
     st = algo.stats.cpu().numpy()
     finite = bool((st == st).all())
@@ -760,7 +801,7 @@ def main():
                                         "traffic_over_compulsory": moved / comp,
                                         "floor_us_at_6p3TBps": moved / 6.3e12 * 1e6}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sys.path.insert(0, str(ROOT / "oracle"))
             from cpu_ppo import time_cpu_iteration
 

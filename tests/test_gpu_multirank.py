@@ -117,7 +117,7 @@ def test_bench_launches_two_ranks(tmp_path):
     env.update(RLKS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--config", "c2", "--envs", "512",
                         "--rollout", "16", "--minibatch", "4096", "--epochs", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-kernel-timing"], cwd=root, env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-kernel-timing"], cwd=root, env=env, capture_output=True, text=True,
                        timeout=110)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]

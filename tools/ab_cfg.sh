@@ -4,7 +4,7 @@ set -e
 C=$1; shift
 O=gpurun_out/ab_cfg; mkdir -p $O
 for L in "$@"; do
-  RLKS_LIB=$PWD/rl-k8s-scheduler_amd/rlks/$L timeout -k 10 300 python3 -u bench.py --config $C --steps 2 --warmup 1 --no-cpu-baseline > $O/${C}_$L.txt 2>&1
+  RLKS_LIB=$PWD/rl-k8s-scheduler_amd/rlks/$L timeout -k 10 300 python3 -u bench.py --config $C --steps 2 --warmup 1 --full --no-cpu-baseline > $O/${C}_$L.txt 2>&1
   python3 -c "
 import json
 d=[json.loads(l) for l in open('$O/${C}_$L.txt') if l.startswith('{')][-1]

@@ -4,7 +4,7 @@
 O=gpurun_out/f1time; mkdir -p $O
 run() {  # name, env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python3 -u bench.py --config c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/$n.txt 2>&1 || { tail -5 $O/$n.txt; return 1; }
+  env "$@" timeout -k 10 300 python3 -u bench.py --config c4 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/$n.txt 2>&1 || { tail -5 $O/$n.txt; return 1; }
   python3 -c "
 import json
 d=[json.loads(l) for l in open('$O/$n.txt') if l.startswith('{')][-1]

@@ -7,7 +7,7 @@ O=gpurun_out/${1:-ranks}
 mkdir -p $O
 for C in c2 c4; do
   RLKS_DIST_BACKEND=gloo timeout -k 10 400 python3 -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --config $C --steps 2 --warmup 1 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --config $C --steps 2 --warmup 1 --full --no-cpu-baseline \
     > $O/bench_${C}_2ranks_gloo_1gpu.log 2>&1
   python3 -c "
 import json
