@@ -264,7 +264,9 @@ int rlks_ppo_grad(const rlks_mlp_desc* desc, const rlks_ppo_coeffs* coeffs, cons
                   double* stats_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 /* Same, launching only the phases in `phases` (profiling / benchmarking: each phase reads what the
- * previous phases left in the workspace). */
+ * previous phases left in the workspace).  Split-fp16: F1A / F1B without a FWD bit run the split F1
+ * kernels and a REDUCE in the same call sums their partials; a call with REDUCE and no F1 phase sums
+ * the partials of the default F1 form (rlks_sf_f1_fused). */
 #define RLKS_PHASE_FWD 1    /* F1: forward + head + loss + dZ2 */
 #define RLKS_PHASE_DW2 2    /* F2: dW2 = dZ2^T H1 (split over rows) */
 #define RLKS_PHASE_DH1 4    /* F3: dH1 = dZ2 W2 -> dZ1 -> dW1, db1 partials */
@@ -290,7 +292,8 @@ int rlks_ppo_grad_profile(const rlks_mlp_desc* desc, const rlks_ppo_coeffs* coef
                           void* workspace_dev, int64_t workspace_bytes, int reps, double* ms_out, void* stream);
 
 /* 1 if a whole split-fp16 gradient of this descriptor runs F1 as one kernel (k_sf_f1: the default up to
- * 4 actions; RLKS_F1_FUSED=1 / RLKS_F1_SPLIT=1 in the environment force either form), else 0 (bench.py
+ * 4 actions; RLKS_F1_FUSED=1 / RLKS_F1_SPLIT=1 in the environment force either form, any other value is
+ * as unset), else 0 (bench.py
  * names the kernels it times and profiles by it).  Not a reference interface: build introspection. */
 int rlks_sf_f1_fused(const rlks_mlp_desc* desc);
 

@@ -1,6 +1,7 @@
-// common.hip — error plumbing and version string of librlks.so
+// common.hip — error plumbing, the runtime switch reader and version string of librlks.so
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
 
 #include "rlks_internal.h"
@@ -14,6 +15,15 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 int fail(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
+}
+
+// The one reader of the library's runtime switches (RLKS_F1_FUSED / RLKS_F1_SPLIT, sgd_sf16.hip
+// sf_f1_fused): on only when the value starts with '1', so NAME=0 and NAME= are off like an unset
+// NAME.  Read at every call, not cached: the tests flip the switches inside one process, and two
+// environment reads against a ~200 us SGD step are not worth a cache with invalidation.
+bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
 }
 
 #ifdef RLKS_DEBUG

@@ -45,10 +45,6 @@ struct rlks_env {
   long long* d_eplog_key;
   unsigned* d_eplog_n;
   double* d_epstat;  // [ceil(n_envs / EPS_LANES)][2] partial (sum, count) of rlks_env_episode_stats
-  // node rollouts in two lane halves (ppo.hip node_rollout): the second half's stream and the fork /
-  // join events, created on first use
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
 namespace rlks {
@@ -58,8 +54,8 @@ constexpr int MAX_TABLE_BYTES = 128 * 1024;  // LDS budget for the staged tables
 
 struct EnvView {
   int N, T, C, max_steps, noise_mode, autoreset, env_offset, track_returns;
-  int lane0, lane_end;  // the lanes a node step / sample launch covers: [lane0, lane_end) (view(): all N);
-                        // N stays the stride of the per-lane arrays
+  int n_trace, n_skip;  // (node-level tables' lengths; here, so that the fields below keep the offsets
+                        // k_node_step_wl's scalar loads were tuned at: profiles/r07_retire)
   uint32_t k0, k1;
   double cpu_lo, span, w_cost, w_lat, scale;
   int32_t* step;
@@ -69,7 +65,7 @@ struct EnvView {
   int32_t* ep_cnt;
   uint32_t* mt;
   // node-level extension; nodes == 0 is the reference env
-  int nodes, pod_cpu, pod_mem, arrival_mode, n_trace, n_skip;
+  int nodes, pod_cpu, pod_mem, arrival_mode;
   uint32_t pod_mag;     // pods on a node = mul_u24(cap - free, pod_mag) >> pod_shift (exact: see view())
   int pod_shift;
   double penalty;
@@ -86,12 +82,9 @@ struct EnvView {
   unsigned* eplog_n;
 };
 
-bool node_step_range(rlks_env* e, int lane0, int lane_end, const int32_t* actions, float* obs, float* rew32,
-                     uint8_t* term, hipStream_t s);  // (env.hip)
-
 inline EnvView view(const rlks_env* e) {
   EnvView v;
-  v.N = e->cfg.n_envs; v.lane0 = 0; v.lane_end = e->cfg.n_envs; v.T = e->cfg.n_rows; v.C = e->cfg.n_clouds; v.max_steps = e->cfg.max_steps;
+  v.N = e->cfg.n_envs; v.T = e->cfg.n_rows; v.C = e->cfg.n_clouds; v.max_steps = e->cfg.max_steps;
   v.noise_mode = e->cfg.noise_mode; v.autoreset = e->cfg.autoreset; v.env_offset = e->cfg.env_offset;
   v.track_returns = e->cfg.skip_returns ? 0 : 1;
   v.k0 = (uint32_t)e->cfg.seed; v.k1 = (uint32_t)(e->cfg.seed >> 32);

@@ -195,6 +195,23 @@ struct Reducer {
       mnext[mslot] += nb;
     }
   }
+  // Fused Adam step `step` on every parameter as its gradient is summed (the tasks are all added); the
+  // new W2 / W1a maxima go to the slots of the step's parity and are tagged step + 1 (tag of step s =
+  // s + 1, 0: none), which step + 1's prep expects: the slots are complete when the reduce is, and the
+  // next prep is a later launch.  false: a weight has more reduce blocks than a slot holds.
+  bool adam(float* p, float* m, float* v, const float* grad, const AdamCo& co, int step, const SfNetW (&w)[2]) {
+    for (int k = 0; k < 4; ++k)
+      if (mnext[k] > SF_PMAX) return false;
+    a.p = p; a.m = m; a.v = v; a.grad = grad; a.co = co;
+    const int par = step & 1;
+    for (int net = 0; net < 2; ++net) {
+      a.slot[2 * net] = w[net].pmax + (par * 2 + 0) * SF_PMAX;
+      a.slot[2 * net + 1] = w[net].pmax + (par * 2 + 1) * SF_PMAX;
+      a.tag[net] = w[net].tag + par;
+    }
+    a.tag_val = (unsigned)step + 1u;
+    return true;
+  }
 };
 
 // fp32 path: per-net stat sums -> RLKS_STAT_* layout
@@ -493,7 +510,7 @@ static SfWs sf_ws_layout(int D, int A, int M, char* base) {
   SfWs w{};
   const int KD = sf_kd(D), tiles = M / 32;  // F2's 32-row tiles
   w.blocks = M / (16 * SF_F1_W);  // F1 workgroups of SF_F1_W x 16 rows
-  w.fa_parts = sf_f1_parts(M, false);
+  w.fa_parts = sf_f1_parts(M, SF_F1_SPLIT);
   w.splits = 1;
   constexpr int F2_MAX_SPLITS = 128;  // F2 row splits per net (one 512-thread workgroup each)
   while (w.splits * 2 <= F2_MAX_SPLITS && tiles % (w.splits * 2) == 0) w.splits *= 2;
@@ -614,14 +631,13 @@ static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* para
     }
     r.M = N; r.D = D;
   }
-  auto forward = [&](const float* x, float* logits, float* values, int M = -1, hipStream_t fs = nullptr) -> int {
+  auto forward = [&](const float* x, float* logits, float* values) -> int {
     if (w) {  // 16-row tiles of both nets (sgd_sf16.hip k_sf_fwd16)
       SfFwdArgs a = r;
       a.x = x;
-      a.M = M < 0 ? N : M;
       a.out[0] = logits;
       a.out[1] = values;
-      return launch_sf_fwd16(a, A, fs ? fs : s);
+      return launch_sf_fwd16(a, A, s);
     }
     for (int net = 0; net < 2; ++net) {
       float* out = net == 0 ? logits : values;
@@ -634,45 +650,6 @@ static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* para
     return RLKS_OK;
   };
   const EnvView v = view(env);
-  // Two lane halves on two streams (opt-in: RLKS_NODE_TWO_STREAMS=1): each half runs
-  // forward -> sample -> node step on its own stream, so that one half's latency-bound node step could
-  // run beside the other half's forward.  Same launches per lane, Philox counters per lane: the same
-  // rollout bit for bit.  Measured at c3 (profiles/r06_node): 12.9-13.0 ms a rollout against 12.7 ms in
-  // one stream -- the half-size forward keeps every CU's wave slots (4 waves per SIMD at 128
-  // registers), so the node step finds none free beside it and the split only adds its overheads.
-  const int half = (N / 2) / 128 * 128;
-  if (w && N >= 8192 && env->cfg.nodes_per_cluster > 0 && env->cfg.n_clouds <= 64 && getenv("RLKS_NODE_TWO_STREAMS")) {
-    if (!env->side) {
-      RLKS_HIP(hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking));
-      RLKS_HIP(hipEventCreateWithFlags(&env->ev_fork, hipEventDisableTiming));
-      RLKS_HIP(hipEventCreateWithFlags(&env->ev_join, hipEventDisableTiming));
-    }
-    RLKS_HIP(hipEventRecord(env->ev_fork, s));
-    RLKS_HIP(hipStreamWaitEvent(env->side, env->ev_fork, 0));
-    const int lo[2] = {0, half}, hi[2] = {half, N};
-    const hipStream_t hs[2] = {s, env->side};
-    for (int t = 0; t < b->T; ++t) {
-      const size_t tN = (size_t)t * N;
-      for (int h = 0; h < 2; ++h) {
-        const size_t o = tN + lo[h];
-        if (int rc = forward(b->obs + o * D, b->logits + o * A, b->values + o, hi[h] - lo[h], hs[h])) return rc;
-        EnvView vh = v;
-        vh.lane0 = lo[h];
-        vh.lane_end = hi[h];
-        if (int rc = launch_sample(vh, b->logits + tN * A, A, explore, b->actions + tN, b->logp + tN, hs[h])) return rc;
-        if (!node_step_range(env, lo[h], hi[h], b->actions + tN, b->obs + (tN + N) * D, b->rewards + tN,
-                             b->dones + tN, hs[h]))
-          return fail(RLKS_ERR_HIP, "node_rollout: lane-range node step");
-      }
-    }
-    for (int h = 0; h < 2; ++h) {
-      const size_t o = (size_t)b->T * N + lo[h];
-      if (int rc = forward(b->obs + o * D, nullptr, b->values + o, hi[h] - lo[h], hs[h])) return rc;
-    }
-    RLKS_HIP(hipEventRecord(env->ev_join, env->side));
-    RLKS_HIP(hipStreamWaitEvent(s, env->ev_join, 0));
-    return RLKS_OK;
-  }
   for (int t = 0; t < b->T; ++t) {
     const size_t tN = (size_t)t * N;
     if (int rc = forward(b->obs + tN * D, b->logits + tN * A, b->values + tN)) return rc;
@@ -878,6 +855,7 @@ struct FusedAdam {
   int step, prev_fused;
   bool apply = true;  // false: the prep uses the previous step's maxima, the reduce only sums (an
                       // all-reduce follows; rlks_ppo_adam_apply then applies Adam)
+  int64_t n = 0;      // parameter count, for the unfused Adam pass of the fp32 / wide paths (sgd_step)
 };
 
 // part: 0 = the whole gradient; 1 = the weight split, F1a, F2 and the reduce of W2 / b2 / W3 / b3 and
@@ -907,28 +885,27 @@ static int sf_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const floa
     const NetPtrs P = net_ptrs_host(params, L, net);
     a.n[net].b2 = P.b2; a.n[net].w3 = P.w3; a.n[net].b3 = P.b3;
   }
-  // F1 (forward, loss, dZ2, dH1 -> dW1 / db1, dW3 / db3) per net; F2 (dW2, db2) for both.  F1 is the
-  // fused kernel for a whole gradient (part 0: rlks_ppo_grad, the fused-Adam SGD step, the multi-rank
-  // step's one-bucket form) where sf_f1_fused says so, else the two kernels F1a, F1b; the overlapped
-  // multi-rank form (part 1 / 2: F1b under the all-reduce) always runs the two
-  const bool fused_f1 = part == 0 && sf_f1_fused(A);
+  // F1 (forward, loss, dZ2, dH1 -> dW1 / db1, dW3 / db3) per net; F2 (dW2, db2) for both.  F1's form is
+  // decided here, once, for the launch and for the reducer's partial count alike:
+  //   part 1 / 2 (the overlapped multi-rank form, F1b under the all-reduce): that part's split kernel;
+  //   F1A / F1B without a FWD bit (profiling: each half reads what a full F1 left in the workspace): the
+  //     split kernels asked for, both nets;
+  //   else (rlks_ppo_grad, the fused-Adam SGD step, the multi-rank step's one-bucket form; also a call
+  //     that only reduces): the fused kernel where sf_f1_fused says so, else both split kernels.
+  const int f1ab = phases & (RLKS_PHASE_F1A | RLKS_PHASE_F1B);
+  SfF1Form f1;
+  if (part != 0) f1 = part == 1 ? SF_F1_A : SF_F1_B;
+  else if (f1ab && !(f_pi || f_vf)) f1 = SfF1Form((f1ab & RLKS_PHASE_F1A ? SF_F1_A : 0) | (f1ab & RLKS_PHASE_F1B ? SF_F1_B : 0));
+  else f1 = sf_f1_fused(A) ? SF_F1_FUSED : SF_F1_SPLIT;
   if (f_pi || f_vf) {
-    const int net0 = f_pi ? 0 : 1, nets = (f_pi && f_vf) ? 2 : 1;
-    if (fused_f1 || part != 0) {
-      if (int rc = launch_sf_f1(a, net0, nets, A, s, fused_f1 ? SF_F1_FUSED : part)) return rc;
-    } else {
-      if (int rc = launch_sf_f1(a, net0, nets, A, s, 3)) return rc;
-    }
+    if (int rc = launch_sf_f1(a, f_pi ? 0 : 1, (f_pi && f_vf) ? 2 : 1, A, s, f1)) return rc;
+  } else if (f1ab) {
+    if (int rc = launch_sf_f1(a, 0, 2, A, s, f1)) return rc;
   }
-  // split F1 halves alone, both nets (profiling: each reads what a full F1 left in the workspace)
-  if (!(f_pi || f_vf) && (phases & (RLKS_PHASE_F1A | RLKS_PHASE_F1B)))
-    if (int rc = launch_sf_f1(a, 0, 2, A, s, (phases & RLKS_PHASE_F1A ? 1 : 0) | (phases & RLKS_PHASE_F1B ? 2 : 0)))
-      return rc;
   if (phases & RLKS_PHASE_DW2)
     if (int rc = launch_sf_dw2(a, w.splits, s)) return rc;
   if (!(phases & RLKS_PHASE_REDUCE)) return RLKS_OK;
-  // F1's partial count: the fused kernel has half the split kernels' workgroups
-  const int f1p = sf_f1_parts(M, fused_f1);
+  const int f1p = sf_f1_parts(M, f1);  // the fused kernel has half the split kernels' workgroups
   Reducer R;
   for (int net = 0; net < 2; ++net) {
     const int An = net == 0 ? A : 1;
@@ -940,7 +917,7 @@ static int sf_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const floa
     }
     if (part != 2) {
       R.add(n.part_w2, grad + o[2], nullptr, SF_W2_PSTRIDE, w.splits, H * H, 2 * net);
-      R.a.t[R.a.ntasks - 1].kq = sf_f2_regs() ? 1 : 0;
+      R.a.t[R.a.ntasks - 1].kq = 1;  // k_sf_dw2r's partial order
       R.add(n.part_b2, grad + o[3], nullptr, H, w.splits, H);
       R.add(n.part_w3, grad + o[4], nullptr, (int64_t)An * H, f1p, An * H);
       if (net == 0) R.add(n.part_b3, grad + o[5], nullptr, An, f1p, An);
@@ -958,19 +935,8 @@ static int sf_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const floa
   }
   if (fa && fa->apply) {  // Adam on every parameter as its gradient is summed; W2 / W1a maxima -> the next prep
     RLKS_REQUIRE(part == 0, RLKS_ERR_ARG, "sf_grad: fused Adam needs the whole gradient");
-    for (int k = 0; k < 4; ++k)
-      RLKS_REQUIRE(R.mnext[k] <= SF_PMAX, RLKS_ERR_UNSUPPORTED, "rlks_ppo_sgd_step: too many reduce blocks per weight");
-    R.a.p = fa->p; R.a.m = fa->m; R.a.v = fa->v; R.a.grad = grad; R.a.co = fa->co;
-    const int par = fa->step & 1;
-    for (int net = 0; net < 2; ++net) {
-      R.a.slot[2 * net] = w.w[net].pmax + (par * 2 + 0) * SF_PMAX;
-      R.a.slot[2 * net + 1] = w.w[net].pmax + (par * 2 + 1) * SF_PMAX;
-    }
-    // the slots are complete when the reduce is (the next prep is a later launch): mark them as
-    // this step's
-    R.a.tag[0] = w.w[0].tag + par;
-    R.a.tag[1] = w.w[1].tag + par;
-    R.a.tag_val = (unsigned)fa->step + 1u;  // tag of step s = s + 1 (0: none), expected by step s + 1's prep
+    RLKS_REQUIRE(R.adam(fa->p, fa->m, fa->v, grad, fa->co, fa->step, w.w), RLKS_ERR_UNSUPPORTED,
+                 "rlks_ppo_sgd_step: too many reduce blocks per weight");
   }
   if (nx && nx->rows > 0) {  // + the next step's gather (blocks after the reduce's)
     NextGather n = *nx;
@@ -1127,30 +1093,18 @@ static AdamCo adam_co(float lr, float beta1, float beta2, float eps, int step) {
   return AdamCo{1.f - beta1, beta2, 1.f - beta2, (float)(lr / bc1), (float)std::sqrt(bc2), eps};
 }
 
-int rlks_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                   float eps, int step, void* stream) {
-  RLKS_REQUIRE(p && g && m && v && n >= 0 && step >= 1, RLKS_ERR_ARG, "rlks_adam_step: bad argument");
+static int adam_pass(float* p, const float* g, float* m, float* v, int64_t n, const AdamCo& co, void* stream) {
+  RLKS_REQUIRE(p && g && m && v && n >= 0, RLKS_ERR_ARG, "rlks_adam_step: bad argument");
   if (n == 0) return RLKS_OK;
-  hipLaunchKernelGGL(k_adam, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     adam_co(lr, beta1, beta2, eps, step));
+  hipLaunchKernelGGL(k_adam, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, co);
   RLKS_LAUNCHED();
   return RLKS_OK;
 }
 
-int rlks_ppo_sgd_step(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, float* params, const float* dyn,
-                      const float* mb, int M, float* grad, double* stats, float* adam_m, float* adam_v, int64_t n_params,
-                      float lr, float beta1, float beta2, float eps, int step, int prev_fused, void* workspace,
-                      int64_t ws_bytes, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  RLKS_REQUIRE(co && params && dyn && mb && grad && adam_m && adam_v && workspace && step >= 1, RLKS_ERR_ARG,
-               "rlks_ppo_sgd_step: bad argument");
-  if (!is_sf(d) || is_wide(d)) {  // unfused: gradient, then Adam
-    if (int rc = rlks_ppo_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream)) return rc;
-    return rlks_adam_step(params, grad, adam_m, adam_v, n_params, lr, beta1, beta2, eps, step, stream);
-  }
-  FusedAdam fa{params, adam_m, adam_v, adam_co(lr, beta1, beta2, eps, step), step, prev_fused ? 1 : 0};
-  return sf_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, RLKS_PHASE_ALL, (hipStream_t)stream,
-                 &fa);
+int rlks_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                   float eps, int step, void* stream) {
+  RLKS_REQUIRE(step >= 1, RLKS_ERR_ARG, "rlks_adam_step: bad argument");
+  return adam_pass(p, g, m, v, n, adam_co(lr, beta1, beta2, eps, step), stream);
 }
 
 // the next step's gather as extra reduce blocks (fused = true), or false: the caller gathers with
@@ -1180,89 +1134,97 @@ static int gather_after(const rlks_mlp_desc* d, const rlks_gather_next* x, void*
                                 x->rows, x->mb_dev, stream);
 }
 
+// What the five SGD-step entry points below share; each is an argument adapter over sgd_step_any.
+struct StepArgs {
+  const rlks_mlp_desc* d;
+  const rlks_ppo_coeffs* co;
+  const float *params, *dyn, *mb;
+  int M;
+  float* grad;
+  double* stats;
+  void* workspace;
+  int64_t ws_bytes;
+  void* stream;
+};
+
+// One SGD step: the gradient of `part` (sf_grad: 0 = whole), Adam in its reduce when fa.apply, and the
+// next step's gather x (or null; taken by part 0 and part 2) in the reduce's launch where that form
+// exists, else as a call of its own after the step.  Off the split-fp16 kernels nothing is fused:
+// the gradient (all of it in part 1), then Adam as a pass of its own, then the gather.
+// bad_arg: the entry point's message for a null argument or step < 1.
+static int sgd_step_any(const StepArgs& a, const char* bad_arg, const FusedAdam& fa, const rlks_gather_next* x,
+                        int part) {
+  if (int rc = check_desc(a.d)) return rc;
+  RLKS_REQUIRE(a.co && a.params && a.dyn && a.mb && a.grad && a.workspace && fa.step >= 1 &&
+                   (!fa.apply || (fa.m && fa.v)), RLKS_ERR_ARG, bad_arg);
+  if (part == 1) x = nullptr;
+  if (!is_sf(a.d) || is_wide(a.d)) {
+    if (part != 2) {
+      if (int rc = rlks_ppo_grad(a.d, a.co, a.params, a.dyn, a.mb, a.M, a.grad, a.stats, a.workspace, a.ws_bytes, a.stream))
+        return rc;
+      if (fa.apply)
+        if (int rc = adam_pass(fa.p, a.grad, fa.m, fa.v, fa.n, fa.co, a.stream)) return rc;
+    }
+    return x ? gather_after(a.d, x, a.stream) : RLKS_OK;
+  }
+  NextGather n;
+  bool fused = false;
+  if (x)
+    if (int rc = next_gather(a.d, x, n, fused)) return rc;
+  if (int rc = sf_grad(a.d, a.co, a.params, a.dyn, a.mb, a.M, a.grad, a.stats, a.workspace, a.ws_bytes, RLKS_PHASE_ALL,
+                       (hipStream_t)a.stream, &fa, fused ? &n : nullptr, part))
+    return rc;
+  return (x && !fused) ? gather_after(a.d, x, a.stream) : RLKS_OK;
+}
+
+// gradient only: the prep reads the previous step's maxima when prev_fused, the reduce only sums
+static FusedAdam grad_only(int step, int prev_fused) {
+  return FusedAdam{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
+}
+
 int rlks_ppo_sgd_step_next(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, float* params, const float* dyn,
                            const float* mb, int M, float* grad, double* stats, float* adam_m, float* adam_v,
                            int64_t n_params, float lr, float beta1, float beta2, float eps, int step, int prev_fused,
                            const rlks_gather_next* x, void* workspace, int64_t ws_bytes, void* stream) {
-  if (!x)
-    return rlks_ppo_sgd_step(d, co, params, dyn, mb, M, grad, stats, adam_m, adam_v, n_params, lr, beta1, beta2, eps,
-                             step, prev_fused, workspace, ws_bytes, stream);
-  if (int rc = check_desc(d)) return rc;
-  NextGather n;
-  bool fused;
-  if (int rc = next_gather(d, x, n, fused)) return rc;
-  if (!fused) {  // the two calls
-    if (int rc = rlks_ppo_sgd_step(d, co, params, dyn, mb, M, grad, stats, adam_m, adam_v, n_params, lr, beta1, beta2,
-                                   eps, step, prev_fused, workspace, ws_bytes, stream))
-      return rc;
-    return gather_after(d, x, stream);
-  }
-  RLKS_REQUIRE(co && params && dyn && mb && grad && adam_m && adam_v && workspace && step >= 1, RLKS_ERR_ARG,
-               "rlks_ppo_sgd_step: bad argument");
-  FusedAdam fa{params, adam_m, adam_v, adam_co(lr, beta1, beta2, eps, step), step, prev_fused ? 1 : 0};
-  return sf_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, RLKS_PHASE_ALL, (hipStream_t)stream,
-                 &fa, &n);
+  const FusedAdam fa{params, adam_m, adam_v, adam_co(lr, beta1, beta2, eps, step), step, prev_fused ? 1 : 0, true,
+                     n_params};
+  return sgd_step_any({d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream},
+                      "rlks_ppo_sgd_step: bad argument", fa, x, 0);
+}
+
+int rlks_ppo_sgd_step(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, float* params, const float* dyn,
+                      const float* mb, int M, float* grad, double* stats, float* adam_m, float* adam_v, int64_t n_params,
+                      float lr, float beta1, float beta2, float eps, int step, int prev_fused, void* workspace,
+                      int64_t ws_bytes, void* stream) {
+  return rlks_ppo_sgd_step_next(d, co, params, dyn, mb, M, grad, stats, adam_m, adam_v, n_params, lr, beta1, beta2, eps,
+                                step, prev_fused, nullptr, workspace, ws_bytes, stream);
 }
 
 // The multi-rank form of rlks_ppo_sgd_step: the gradient (its prep reading the previous step's
 // maxima when prev_fused), then, after the caller's all-reduce, Adam as a reduce over one partial
 // (the summed gradient) that also leaves the new maxima and the step tag, so no SGD step needs the
 // separate weight-max pass.  Same arithmetic as k_adam / the fused reduce: bit-identical parameters.
-int rlks_ppo_grad_step(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* params, const float* dyn,
-                       const float* mb, int M, float* grad, double* stats, int step, int prev_fused, void* workspace,
-                       int64_t ws_bytes, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  RLKS_REQUIRE(co && params && dyn && mb && grad && workspace && step >= 1, RLKS_ERR_ARG,
-               "rlks_ppo_grad_step: bad argument");
-  if (!is_sf(d) || is_wide(d))
-    return rlks_ppo_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream);
-  FusedAdam fa{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
-  return sf_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, RLKS_PHASE_ALL, (hipStream_t)stream,
-                 &fa);
-}
-
 int rlks_ppo_grad_step_next(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* params, const float* dyn,
                             const float* mb, int M, float* grad, double* stats, int step, int prev_fused,
                             const rlks_gather_next* x, void* workspace, int64_t ws_bytes, void* stream) {
-  if (!x)
-    return rlks_ppo_grad_step(d, co, params, dyn, mb, M, grad, stats, step, prev_fused, workspace, ws_bytes, stream);
-  if (int rc = check_desc(d)) return rc;
-  NextGather n;
-  bool fused;
-  if (int rc = next_gather(d, x, n, fused)) return rc;
-  if (!fused) {
-    if (int rc = rlks_ppo_grad_step(d, co, params, dyn, mb, M, grad, stats, step, prev_fused, workspace, ws_bytes,
-                                    stream))
-      return rc;
-    return gather_after(d, x, stream);
-  }
-  RLKS_REQUIRE(co && params && dyn && mb && grad && workspace && step >= 1, RLKS_ERR_ARG,
-               "rlks_ppo_grad_step: bad argument");
-  FusedAdam fa{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
-  return sf_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, RLKS_PHASE_ALL, (hipStream_t)stream,
-                 &fa, &n);
+  return sgd_step_any({d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream},
+                      "rlks_ppo_grad_step: bad argument", grad_only(step, prev_fused), x, 0);
+}
+
+int rlks_ppo_grad_step(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* params, const float* dyn,
+                       const float* mb, int M, float* grad, double* stats, int step, int prev_fused, void* workspace,
+                       int64_t ws_bytes, void* stream) {
+  return rlks_ppo_grad_step_next(d, co, params, dyn, mb, M, grad, stats, step, prev_fused, nullptr, workspace, ws_bytes,
+                                 stream);
 }
 
 int rlks_ppo_grad_step_part(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* params, const float* dyn,
                             const float* mb, int M, float* grad, double* stats, int step, int prev_fused, int part,
                             const rlks_gather_next* x, void* workspace, int64_t ws_bytes, void* stream) {
-  if (int rc = check_desc(d)) return rc;
+  if (int rc = check_desc(d)) return rc;  // (ahead of the part check, as it always was)
   RLKS_REQUIRE(part == 1 || part == 2, RLKS_ERR_ARG, "rlks_ppo_grad_step_part: part must be 1 or 2");
-  RLKS_REQUIRE(co && params && dyn && mb && grad && workspace && step >= 1, RLKS_ERR_ARG,
-               "rlks_ppo_grad_step_part: bad argument");
-  if (!is_sf(d) || is_wide(d)) {  // no split form: everything in part 1
-    if (part == 2) return x ? gather_after(d, x, stream) : RLKS_OK;
-    return rlks_ppo_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream);
-  }
-  FusedAdam fa{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
-  NextGather n;
-  bool fused = false;
-  if (x && part == 2)
-    if (int rc = next_gather(d, x, n, fused)) return rc;
-  if (int rc = sf_grad(d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, RLKS_PHASE_ALL, (hipStream_t)stream,
-                       &fa, fused ? &n : nullptr, part))
-    return rc;
-  return (x && part == 2 && !fused) ? gather_after(d, x, stream) : RLKS_OK;
+  return sgd_step_any({d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream},
+                      "rlks_ppo_grad_step_part: bad argument", grad_only(step, prev_fused), x, part);
 }
 
 int rlks_ppo_adam_apply(const rlks_mlp_desc* d, float* params, const float* grad, float* adam_m, float* adam_v,
@@ -1291,17 +1253,8 @@ int rlks_ppo_adam_apply(const rlks_mlp_desc* d, float* params, const float* grad
     R.add(g + o[4], g + o[4], nullptr, 0, 1, An * H);
     R.add(g + o[5], g + o[5], nullptr, 0, 1, An);
   }
-  for (int k = 0; k < 4; ++k)
-    RLKS_REQUIRE(R.mnext[k] <= SF_PMAX, RLKS_ERR_UNSUPPORTED, "rlks_ppo_adam_apply: too many blocks per weight");
-  R.a.p = params; R.a.m = adam_m; R.a.v = adam_v; R.a.grad = grad; R.a.co = adam_co(lr, beta1, beta2, eps, step);
-  const int par = step & 1;
-  for (int net = 0; net < 2; ++net) {
-    R.a.slot[2 * net] = w.w[net].pmax + (par * 2 + 0) * SF_PMAX;
-    R.a.slot[2 * net + 1] = w.w[net].pmax + (par * 2 + 1) * SF_PMAX;
-  }
-  R.a.tag[0] = w.w[0].tag + par;
-  R.a.tag[1] = w.w[1].tag + par;
-  R.a.tag_val = (unsigned)step + 1u;
+  RLKS_REQUIRE(R.adam(params, adam_m, adam_v, grad, adam_co(lr, beta1, beta2, eps, step), step, w.w),
+               RLKS_ERR_UNSUPPORTED, "rlks_ppo_adam_apply: too many blocks per weight");
   hipLaunchKernelGGL(k_reduce, dim3(R.blocks), dim3(256), 0, (hipStream_t)stream, R.a);
   RLKS_LAUNCHED();
   return RLKS_OK;

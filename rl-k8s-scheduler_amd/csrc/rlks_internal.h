@@ -32,6 +32,9 @@ int fail(int code, const std::string& msg);
 
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// runtime form switch (common.hip): true only when the environment variable's value starts with '1'
+bool env_on(const char* name);
+
 // ----------------------------------------------------------------------------- debug checks
 // `make -C csrc debug` (librlks_debug.so, -DRLKS_DEBUG): device-side bounds checks on the indexing
 // a corrupted state or a wrong shape would send out of bounds (node-state chunks and nodes, the

@@ -111,16 +111,13 @@ int launch_sf_fwd16(const SfFwdArgs& a, int A, hipStream_t s);
 
 int sf_kd(int D);
 int launch_sf_prep(const SfPrepArgs& a, hipStream_t s);
-// halves: 1 = F1a (k_sf_fwd), 2 = F1b (k_sf_bwd), 3 = both, SF_F1_FUSED = the fused kernel (k_sf_f1)
-constexpr int SF_F1_FUSED = 7;
-int launch_sf_f1(const SfArgs& a, int net0, int nets, int A, hipStream_t s, int halves = 3);  // needs M % 256 == 0
-int launch_sf_dw2(const SfArgs& a, int splits, hipStream_t s);
-// whether F2 is k_sf_dw2r (H1 in registers; its dW2 partials in [k / 4][n][4] order, the default)
-// rather than round 3-5's k_sf_dw2 ([n][k] partials; RLKS_F2_IMAGE=1, kept for same-box A/B runs)
-bool sf_f2_regs();
+// the form F1 runs in: the split kernels F1a (k_sf_fwd) and / or F1b (k_sf_bwd), or the fused kernel (k_sf_f1)
+enum SfF1Form { SF_F1_A = 1, SF_F1_B = 2, SF_F1_SPLIT = SF_F1_A | SF_F1_B, SF_F1_FUSED = 4 };
+int launch_sf_f1(const SfArgs& a, int net0, int nets, int A, hipStream_t s, SfF1Form form);  // needs M % 256 == 0
+int launch_sf_dw2(const SfArgs& a, int splits, hipStream_t s);  // k_sf_dw2r: dW2 partials in [k / 4][n][4] order
 // F1's partials per net (one per F1 workgroup): dW1 / db1, and dW3 / db3 / stats; the workspace holds
 // the split kernels' count (the larger), the fused kernel writes half as many
-int sf_f1_parts(int M, bool fused);
+int sf_f1_parts(int M, SfF1Form form);
 // whether a whole gradient (part 0: one rank, or the multi-rank step's one-bucket form) runs the fused
 // F1 kernel at A actions: by default up to 4 actions; RLKS_F1_FUSED=1 / RLKS_F1_SPLIT=1 force it
 // 

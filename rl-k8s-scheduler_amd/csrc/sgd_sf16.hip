@@ -21,14 +21,13 @@
 //     dH1 = dZ2 W2             A = dZ2^T accumulator (transposes to rows-in-registers)
 //     Z1 = Xa W1a^T, dZ1 = dH1 (1 - H1^2)
 //     dW1a^T = Xa^T dZ1        B = dZ1 accumulator; row D of dW1a is db1
-//   F2 (k_sf_dw2): dW2 = dZ2^T H1 over the rows, H1 recomputed (rows in registers) as the B
-//     operand, dZ2^T tiles staged through registers into LDS pre-split with the global max|dZ2|
-//     scale; db2 from the same loads.  Row splits write fp32 partials, summed in a fixed order by k_reduce.
+//   F2 (k_sf_dw2r): dW2^T = H1^T dZ2 over the rows, H1 recomputed (its Z1 accumulator, in registers)
+//     as the A operand, F1a's split dZ2 tiles staged through registers into an LDS image read back
+//     transposed; db2 from the same loads.  Row splits write fp32 partials, summed in a fixed order by k_reduce.
 //
 // Reference semantics: RLlib FCNet [256, 256] tanh, vf_share_layers=False, PPO loss as in
 // mlp_fwd.hip (train_ppo.py:9-31; RLlib third-party).
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #include "sgd_sf16.h"
@@ -911,14 +910,15 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   else f1a_body<1, 1, KD, W, P>(g, ng.y);
 }
 
-int sf_f1_parts(int M, bool fused) { return M / (16 * (fused ? SF_F1F_W : SF_F1_W)); }
+int sf_f1_parts(int M, SfF1Form f) { return M / (16 * (f == SF_F1_FUSED ? SF_F1F_W : SF_F1_W)); }
 // F1a + F1b as one kernel (k_sf_f1) for a whole gradient by default at up to 4 actions (16 columns of
 // Xa): with F2 = k_sf_dw2r and the no-SLP build it is the faster form there (c4 +1.3-2.1%, three same-box
 // alternations, profiles/r06_fusedab); at 8 actions the two kernels stay (c3 -0.2 to -3.9% fused).
-// RLKS_F1_FUSED=1 / RLKS_F1_SPLIT=1 force either form (A/B runs, the tests' references).
+// RLKS_F1_FUSED=1 / RLKS_F1_SPLIT=1 force either form (A/B runs, the tests' references); these two are
+// the library's only runtime form switches (env_on, common.hip).
 bool sf_f1_fused(int A) {
-  if (getenv("RLKS_F1_FUSED")) return true;
-  if (getenv("RLKS_F1_SPLIT")) return false;
+  if (env_on("RLKS_F1_FUSED")) return true;
+  if (env_on("RLKS_F1_SPLIT")) return false;
   return A <= 4;
 }
 
@@ -1115,19 +1115,55 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 }
 
 // ----------------------------------------------------------------------------- F2
-// dW2 = dZ2^T H1 over a row range as a tiled split-fp16 GEMM: C [256 n][256 k] per workgroup (512
-// threads, 8 waves of 64 n x 128 k = 2 x 4 v_mfma_f32_32x32x16_f16 tiles: 128 accumulator registers,
-// two waves per SIMD), K = the rows, in chunks of 32, double-buffered in LDS:
-//   A = dZ2^T chunk: F1a's fp32 dZ2 (two 16-row tiles in its lane order), loaded into registers one
-//     chunk ahead, split with the step's max |dZ2| scale; db2 from the same loads;
-//   B = H1 chunk, produced by the workgroup: wave w forms Z1 = Xa W1a^T for the chunk's 32 rows and
-//     hidden units k = 32 w + 0..31 (v_mfma_f32_16x16x16_f16, X scaled by F1a's per-tile exponent),
-//     tanh, split at 2^14.
-// Chunk c + 1's operands are produced after chunk c's MFMAs are issued, in the same basic block (the
-// scheduler interleaves the two), into the other buffer; one barrier per chunk.  Round 2's F2 (eight
-// waves of 256 n x 32 k, H1 in registers) read every A fragment -> wait -> MFMA: 30% MFMA-busy
-// (profiles/r03c).  A 1,024-thread version of this kernel (64 x 64 per wave) spilled at its
-// 128-register budget, and each spill reload waited for the prefetches (vmcnt counts in issue order).
+// dW2^T = H1^T dZ2 over a row range (k_sf_dw2r): grid (splits, 2 nets) x 512 threads; split z covers the
+// 32-row chunks [z tps, (z + 1) tps).  Eight waves of 32 hidden units k x 256 outputs n each (8
+// v_mfma_f32_32x32x16_f16 tiles, 128 accumulator registers, two waves per SIMD); K = the rows, a chunk
+// of 32 (two k-steps s of 16) at a time.
+//   A = H1 of the wave's own hidden units k = 32 w + (l & 31), in registers: Z1 = Xa W1a^T of the
+//     chunk's 32 rows on v_mfma_f32_32x32x8_f16 (Xa as F1a split it, SfArgs::xsp), tanh, split; the
+//     accumulator's rows acc_row(8 s + j) = 16 s + 8 (j >> 2) + 4 h + (j & 3) (h = l >> 5) are k-step
+//     s's K order, so the fragment is used as it stands.
+//   B = the dZ2 chunk, staged by all eight waves into a double-buffered LDS image and read back
+//     transposed in the same K order.
+// Every wave issues its MFMAs of chunk c beside its own production of chunk c + 1 (its share of the
+// dZ2 image, its H1); one barrier per chunk.
+//
+// dZ2 image (halves), per buffer: [plane hi, lo][32 rows m][F2_AROW], n contiguous.  Rows are padded by
+// 32 halves, so that a transposed read's 4 rows x 32 columns land on 4 disjoint 16-bank windows.
+// Within each 32-column block the 8-byte quads sit at position quad ^ 2 ((m >> 2) & 3): the 4 rows of
+// a transposed read share one XOR, and the stores of 16 consecutive rows spread over all banks
+// (profiles/r03k: 20% of CU cycles were LDS bank conflicts without it).  Unswizzled along n and s,
+// every fragment address is one per-lane base plus immediates.
+//   stores: wave w moves columns 32 w + 0..31 of the chunk's two 16-row tiles.  F1a left dZ2 in its
+//     lane order (SfNet::dz2s): piece i = 2 tile + plane of lane l holds halves j of row m = 16 tile +
+//     (l & 15), columns n = 32 w + 16 (j >> 2) + 4 (l >> 4) + (j & 3), i.e. quads l >> 4 and
+//     (l >> 4) + 4 of the row's block; loaded one chunk ahead by buffer loads (an SGPR resource, the
+//     chunk offset in an SGPR and one 32-bit lane offset: a 64-bit address pair per load cost the
+//     registers that made the kernel spill).  db2 comes from the same loads.
+//   transposed reads (tr_read, ds_read_b64_tr_b16): lane 4 q + p of its 16-lane group addresses row
+//     16 s + 4 h + q (+ 8 for the second read), columns 32 ob + 16 ((l >> 4) & 1) + 4 p of output
+//     block ob; the two reads' 8 elements are rows 16 s + 8 (j >> 2) + 4 h + (j & 3), j = 0..7, of
+//     column n = 32 ob + (l & 31): the K order above.
+//
+// Scales.  F1a splits each 16-row tile T of dZ2 at its own 2^e_T (SfNet::tile_edz; 120 for an all-zero
+// tile).  With E = min e_T over the workgroup's tiles, the H1 rows of tile T are split at
+// 2^(14 + E - e_T) (<= 2^14), so every product carries 2^(14 + E) and the accumulators are unscaled
+// once at the end.  A chunk's odd tile arrives negated from F1a and odd splits run on -H1 (tile_sign):
+// both signs are folded into the H1 scale and the unscale.
+//
+// Partials.  An accumulator quad holds 4 consecutive k of one n, so split z's dW2 partial is written
+// in [k / 4][n][4] order (16-byte stores, 512 contiguous bytes per half-wave); the reduce maps it back
+// to [n][k] (RedTask::kq).
+//
+// Earlier forms (the last one's code: commit 61b17e2).  Round 2 also held H1 in
+// registers (eight waves of 256 n x 32 k) but read every dZ2 fragment -> wait -> MFMA: 30% MFMA-busy
+// (profiles/r03c).  Rounds 3-5 kept both operands as LDS images (C [256 n][256 k] per workgroup,
+// waves of 64 n x 128 k) and placed the shared production ping-pong: waves 0-3's MFMAs beside waves
+// 4-7's production, then the reverse, a barrier after each.  It was bound by that pairing, each
+// phase as long as the slower partner (profiles/r05_f2), and its 1,024-thread variant (64 x 64 per
+// wave) spilled at the 128-register budget, each spill reload waiting for the prefetches in flight
+// (vmcnt counts in issue order).  This kernel needs no H1 image and no pairing: same box, c4 F2
+// 55.1-55.2 -> 49.9-50.2 us, c3 78.0 -> 75.8 us (profiles/r06_f2regs).
 typedef __fp16 hf4_t __attribute__((vector_size(8)));
 // ds_read_b64_tr_b16 (T10): per 16-lane group, 4 rows x 16 columns of 16-bit elements, lane i of
 // the group gets column i (row q in element q); EXEC must be all ones
@@ -1138,357 +1174,15 @@ __device__ __forceinline__ h4 tr_read(const _Float16* p) {
 #ifdef RLKS_STAMPS
 // diagnostic build only (tools/stamps.py): F2 phase cycles of lane 0 of every wave,
 // [net][split][wave][prologue, MFMA issue, production, barrier waits, epilogue, start]
+// (k_sf_dw2r takes no stamps yet: the array reads zero)
 __device__ unsigned long long g_f2_stamps[2][128][16][6];
-#define F2_NOW() __builtin_amdgcn_s_memtime()
 #endif
 constexpr int F2_THREADS = 512;
-// LDS images (halves), per buffer: A = dZ2 chunk [plane hi, lo][32 m][F2_AROW] (n contiguous, rows
-// padded by 32 halves: the transposed fragment reads of 4 rows x 32 columns land on 4 disjoint
-// 16-bank windows; 8-byte quads XOR 2 ((m >> 2) & 3) within each 32-column block for the stores), B = H1 chunk [plane][s 2][256 k][16] (16-byte piece h of row k
-// at slot h ^ ((k >> 3) & 1): conflict-free ds_read_b128).  Unswizzled along n, s and k-blocks, every
-// fragment address is one per-lane base plus immediates.
 constexpr int F2_AROW = HID + 32;
 constexpr int F2_APLANE = 32 * F2_AROW;
-constexpr int F2_BPLANE = 2 * HID * 16;
-constexpr int F2_BUF = 2 * F2_APLANE + 2 * F2_BPLANE;
+constexpr int F2R_ABUF = 2 * F2_APLANE;  // halves per buffer: the dZ2 image's hi and lo planes
 constexpr int F2_MAX_TILES = 2 * 256;  // 16-row tiles per F2 workgroup (tiles_per_split <= 256 chunks)
 
-// grid (splits, 2 nets) x 512 threads; split z covers 32-row chunks [z tps, (z + 1) tps).
-// dZ2 arrives split by F1a, each 16-row tile T at its own scale 2^e_T; the H1 rows of tile T are
-// split at 2^(14 + E - e_T), E = min over the workgroup's tiles, so that every product carries
-// 2^(14 + E) (unscaled at the end).  Production of chunk c + 1 (copy of its dZ2 pieces into the A
-// image, db2, and H1: wave w forms hidden units k = 32 w + 0..31) is shared by all eight waves and
-// placed ping-pong: per chunk c, phase 1 = {waves 0-3: MFMAs of c, 4-7: production}, phase 2 =
-// {0-3: production, 4-7: MFMAs of c}, a barrier after each, so that each SIMD's VALU work runs
-// beside its partner wave's MFMAs.
-template <int KD, int P>
-__global__ __launch_bounds__(F2_THREADS) void k_sf_dw2(SfArgs g) {
-  const SfNet& N = g.n[blockIdx.y];
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  _Float16* sm = reinterpret_cast<_Float16*>(lds);  // [2 buf][F2_BUF]
-  const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = l & 15, gq = l >> 4, wm = w >> 1, wn = w & 1, r = l & 31, h = l >> 5;
-  const bool first = w < 4;  // waves 0-3: MFMAs in phase 1; 4-7: in phase 2
-  const int D = g.D, stride = g.x_stride;
-  int t0 = blockIdx.x * g.tiles_per_split, t1 = t0 + g.tiles_per_split;
-  if (!dcheck(t1 <= g.M / 32, DC_SGD_TILE, t1)) t0 = t1 = 0;
-  const int nk = t1 - t0;
-
-  // F1a's X and dZ2 exponents of the workgroup's 16-row tiles -> LDS (read per chunk from there, not
-  // by a global load among the prefetches); E = min e_T (F1a stores 120 for an all-zero tile)
-  int* sEx = reinterpret_cast<int*>(sm + 2 * F2_BUF);  // [2 (t1 - t0)] X exponents, then dZ2 exponents
-  int* sEd = sEx + F2_MAX_TILES;
-  int emin = 120;
-  for (int i = tid; i < 2 * nk; i += F2_THREADS) {
-    sEx[i] = N.tile_ex[2 * t0 + i];
-    const int e = N.tile_edz[2 * t0 + i];
-    sEd[i] = e;
-    emin = min(emin, e);
-  }
-  __shared__ float s_emin[F2_THREADS / 64];
-  emin = (int)-wave_max((float)-emin);
-  if (l == 0) s_emin[w] = (float)emin;
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < F2_THREADS / 64; ++i) emin = min(emin, (int)s_emin[i]);
-  const int E = __builtin_amdgcn_readfirstlane(emin);
-  // this split's sign (tile_sign: odd splits run their products on -H1 and negate the partial back)
-  const float ssgn = tile_sign(blockIdx.x);
-  const float unscale = ssgn * pow2(-14 - E);
-
-  // per-lane fragment bases (halves within a buffer):
-  //   A (transposed reads): lane 4 q + p of its 16-lane group addresses row 4 h + q (+ 16 s, + 8 for
-  //   the second read), columns 64 wm + 32 i + 16 ((l >> 4) & 1) + 4 p; K order of k-step s: rows
-  //   16 s + 8 (j >> 2) + 4 h + (j & 3) (the MFMA accumulator row order the B image follows)
-  //   B: column k = 128 wn + 32 j + r, piece h
-  //   (A image quads XOR-swizzled by 2 ((m >> 2) & 3): the 4 rows of a transposed read share one XOR,
-  //   and the dZ2 stores of 16 consecutive rows spread over all banks; profiles/r03k: 20% of CU cycles
-  //   were LDS bank conflicts without it)
-  const int aq = (4 * ((l >> 4) & 1) + (l & 3)) ^ (2 * h);  // quad within the 8-quad block, rows 4 h + q
-  const int abase = (4 * h + ((l & 15) >> 2)) * F2_AROW + 4 * aq + 64 * wm;
-  const int abase8 = (4 * h + ((l & 15) >> 2) + 8) * F2_AROW + 4 * (aq ^ 4) + 64 * wm;  // rows + 8
-  const int bbase = 2 * F2_APLANE + (128 * wn + r) * 16 + 8 * (h ^ ((r >> 3) & 1));
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-  auto mfma_chunk = [&](const _Float16* b) {  // A fragments of both i, then B one j at a time (24 registers)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      h8 ah[2], al[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const _Float16* pa = b + abase + s * 16 * F2_AROW + 32 * i;
-        const _Float16* pa8 = b + abase8 + s * 16 * F2_AROW + 32 * i;
-        const h4 a0 = tr_read(pa), a1 = tr_read(pa8);
-        const h4 c0 = tr_read(pa + F2_APLANE), c1 = tr_read(pa8 + F2_APLANE);
-        ah[i] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-        al[i] = __builtin_shufflevector(c0, c1, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const _Float16* pb = b + bbase + s * HID * 16 + 32 * 16 * j;
-        const h8 bh = *reinterpret_cast<const h8*>(pb), bl = *reinterpret_cast<const h8*>(pb + F2_BPLANE);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i][j] = mmaP<P>(ah[i], al[i], bh, bl, acc[i][j]);
-      }
-    }
-  };
-
-  // ---- dZ2 pieces: wave w takes n-step w of both 16-row tiles T2 and both planes (hi, lo): piece
-  // i = 2 T2 + plane of lane l holds halves j at row m = 16 T2 + c, columns n = 32 w + 16 (j >> 2) +
-  // 4 gq + (j & 3) (F1a's layout, loaded one chunk ahead).  (Buffer loads: an SGPR resource, the
-  // chunk offset in an SGPR and one 32-bit lane offset, instead of a 64-bit address pair per load,
-  // which cost the registers that made this kernel spill.)
-  const __amdgpu_buffer_rsrc_t dz_rsrc = __builtin_amdgcn_make_buffer_rsrc(N.dz2s, (short)0, 0x7fffffff, 0x00020000);
-  const int dz_lane = 2 * (w * 1024 + l * 8);  // bytes
-  h8 dp[4];
-  auto load_dz = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      dp[i] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(
-                                         dz_rsrc, dz_lane, t * (32 * HID * 4) + (i >> 1) * (16 * HID * 4) + (i & 1) * 1024, 0));
-  };
-  float db2[8] = {};  // dZ2 of this lane's columns, summed over its rows
-  auto store_dz = [&](_Float16* img, float s0, float s1) {  // s0, s1: 2^-e of the two tiles (0: not counted)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float sc = (i >> 1) ? s1 : s0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) db2[j] = fmaf((float)dp[i][j], sc, db2[j]);
-      // quads 8 w + gq and 8 w + gq + 4 of row m = 16 T2 + c, XOR 2 ((m >> 2) & 3)
-      const int off = (i & 1) * F2_APLANE + (16 * (i >> 1) + c) * F2_AROW + 32 * w;
-      const int sw = 2 * ((c >> 2) & 3);
-      *reinterpret_cast<h4*>(img + off + 4 * (gq ^ sw)) = __builtin_shufflevector(dp[i], dp[i], 0, 1, 2, 3);
-      *reinterpret_cast<h4*>(img + off + 4 * ((gq + 4) ^ sw)) = __builtin_shufflevector(dp[i], dp[i], 4, 5, 6, 7);
-    }
-  };
-
-  // ---- H1 of a chunk as one 32 x 32 block per wave: Z1 (rows m of the chunk, hidden units k =
-  // 32 w + (l & 31)) = Xa W1a^T on v_mfma_f32_32x32x8_f16, K = 8 columns of Xa = [X | 1 | 0] per MFMA
-  // (D + 1 = 7 at 2 actions: one K step, no padding), three products; B = W1a rows k (loaded once),
-  // A = the chunk's X rows (one 16-byte piece per lane and K step, loaded a chunk ahead, the selects
-  // at use); F1a's X and dZ2 exponents of its two 16-row tiles, loaded a chunk ahead
-  constexpr int KB = KD / 8;
-  const int kh = 32 * w + r;  // this lane's hidden unit
-  // (at KD = 32 the fragments are reloaded at every production, ahead of the dZ2 pieces: kept for
-  // the whole kernel they make it spill)
-  h4 wh[KB], wl[KB];
-  auto load_w1 = [&]() {
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      wh[kb] = *reinterpret_cast<const h4*>(N.w1h + kh * KD + 8 * kb + 4 * h);
-      wl[kb] = *reinterpret_cast<const h4*>(N.w1l + kh * KD + 8 * kb + 4 * h);
-    }
-  };
-  if constexpr (KB <= 2) load_w1();
-  const float inv_w1 = N.sc[1];
-  v4f xr[KB];
-  int2 xe, de;
-  const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.x), (short)0, 0x7fffffff, 0x00020000);
-  auto load_x = [&](int t) {
-    xe = *reinterpret_cast<const int2*>(sEx + 2 * (t - t0));
-    de = *reinterpret_cast<const int2*>(sEd + 2 * (t - t0));
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      const int base = 8 * kb + 4 * h, pb = base < stride - 4 ? base : stride - 4;
-      xr[kb] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, 4 * (r * stride + pb), 4 * t * 32 * stride, 0));
-    }
-  };
-  // Z1 row m = acc_row(q) -> B image k-step m >> 4, position 8 h + 4 (q >> 2 & 1) + (q & 3) (bits 2 and 3
-  // of m swapped), hidden unit kh (16-byte piece h at slot h ^ ((kh >> 3) & 1))
-  const int hoff = 2 * F2_APLANE + kh * 16 + 8 * (h ^ ((kh >> 3) & 1));
-  auto store_h1 = [&](_Float16* img) {
-    // X scale of the chunk from F1a's per-tile exponents (the larger max: the smaller exponent)
-    const int ex = min(xe.x, xe.y);
-    const float sx = ssgn * pow2(ex), k_z1 = ssgn * inv_w1 * pow2(-ex) * SF_2LOG2E;
-    f32x16 z;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) z[q] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      const int base = 8 * kb + 4 * h;
-      const bool inrow = base < stride - 4;
-      h4 xh, xl;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int d = base + j;
-        _Float16 a, b;
-        split1(fmaf(xr[kb][j], (d < D && inrow) ? sx : 0.f, d == D ? sx : 0.f), a, b);
-        xh[j] = a;
-        xl[j] = b;
-      }
-      if constexpr (P != 1) {
-        z = __builtin_amdgcn_mfma_f32_32x32x8f16(xl, wh[kb], z, 0, 0, 0);
-        z = __builtin_amdgcn_mfma_f32_32x32x8f16(xh, wl[kb], z, 0, 0, 0);
-      }
-      z = __builtin_amdgcn_mfma_f32_32x32x8f16(xh, wh[kb], z, 0, 0, 0);
-    }
-    // rows of tile 2t + (q >> 3): H1 split at 2^(14 + E - e_T) (<= 2^14)
-    // (the chunk's odd tile arrives negated from F1a: -hs1 undoes it)
-    const float hs0 = ssgn * pow2(14 + E - de.x), hs1 = -ssgn * pow2(14 + E - de.y);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float hs = i < 2 ? hs0 : hs1;
-      float x[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = fmaf(-2.f * hs, tanh_r(z[4 * i + j] * k_z1), hs);
-      unsigned a0, b0, a1, b1;
-      split2(x[0], x[1], a0, b0);
-      split2(x[2], x[3], a1, b1);
-      const h4 hh = __builtin_bit_cast(h4, make_uint2(a0, a1)), hl = __builtin_bit_cast(h4, make_uint2(b0, b1));
-      const int off = hoff + (i >> 1) * HID * 16 + 4 * (i & 1);
-      *reinterpret_cast<h4*>(img + off) = hh;
-      *reinterpret_cast<h4*>(img + off + F2_BPLANE) = hl;
-    }
-  };
-  // production of the loaded chunk into img; counted: add its dZ2 to db2
-  auto produce = [&](_Float16* img, bool counted) {
-    if constexpr (KB > 2) load_w1();
-    const float s0 = counted ? pow2(-de.x) : 0.f, s1 = counted ? -pow2(-de.y) : 0.f;  // (odd tile: negated)
-    store_dz(img, s0, s1);
-    store_h1(img);
-  };
-  // barrier without __syncthreads()'s fence (which would wait for the prefetches in flight: s_waitcnt
-  // vmcnt(0)); the LDS stores need only lgkmcnt(0).  Scheduling barriers on both sides: the scheduler
-  // otherwise moves each phase's VALU into the other phase (e.g. the X split into the MFMA phase,
-  // where it waits for the X loads).
-  auto phase_barrier = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-#ifdef RLKS_STAMPS
-  unsigned long long ts0 = F2_NOW(), tph[5] = {0ull, 0ull, 0ull, 0ull, 0ull}, tq = ts0;
-#define F2_STAMP(i) { const unsigned long long tn = F2_NOW(); tph[i] += tn - tq; tq = tn; }
-#else
-#define F2_STAMP(i)
-#endif
-  if (nk > 0) {
-    load_dz(t0);
-    load_x(t0);
-    produce(sm, true);
-    load_dz(min(t0 + 1, t1 - 1));
-    load_x(min(t0 + 1, t1 - 1));
-  }
-  __syncthreads();
-  F2_STAMP(0);
-  if constexpr (KD > 16) {
-    // KD = 32 (8 actions): one loop for both halves, [MFMAs of chunk ci | barrier | production of chunk
-    // ci + 1 + off | barrier], the second half (off = 1) one phase behind after a production of chunk 1
-    // of its own, so that each SIMD still pairs one wave's MFMAs with its partner's production.  (With a
-    // loop per half the two compiled to different code and the second half's production ran at half the
-    // first half's speed, profiles/r05_f2; here this form also avoids that instance's 10 spilled
-    // registers: c3 F2 86.5 -> 84.8 µs.  At KD = 16 the two loops stay: c4 66-68 vs 69-71 µs.)  The
-    // production runs at the last chunks too, redoing one into the idle buffer uncounted.
-    const int off = first ? 0 : 1;
-    if (!first) {
-      produce(sm + F2_BUF, 1 < nk);
-      load_x(min(t0 + 2, t1 - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      load_dz(min(t0 + 2, t1 - 1));
-      F2_STAMP(2);
-      phase_barrier();
-      F2_STAMP(3);
-    }
-    for (int ci = 0; ci < nk; ++ci) {
-      mfma_chunk(sm + (ci & 1) * F2_BUF);
-      F2_STAMP(1);
-      phase_barrier();
-      F2_STAMP(3);
-      const int cn = ci + 1 + off;  // the chunk this production makes
-      produce(sm + (cn & 1) * F2_BUF, cn < nk);
-      load_x(min(t0 + cn + 1, t1 - 1));  // (before the dZ2 pieces: a spill reload for these
-      __builtin_amdgcn_sched_barrier(0);  // addresses would otherwise wait for them)
-      load_dz(min(t0 + cn + 1, t1 - 1));
-      F2_STAMP(2);
-      phase_barrier();
-      F2_STAMP(3);
-    }
-    if (first) {  // the second half's extra phase
-      phase_barrier();
-      F2_STAMP(3);
-    }
-  } else if (first) {
-    // (one loop per half, so that the phases' state stays in registers; the production runs at the last
-    // chunk too, redoing it into the idle buffer uncounted: unconditional, so that the compiler keeps
-    // the prefetches where they are)
-    for (int ci = 0; ci < nk; ++ci) {
-      mfma_chunk(sm + (ci & 1) * F2_BUF);
-      F2_STAMP(1);
-      phase_barrier();
-      F2_STAMP(3);
-      produce(sm + ((ci + 1) & 1) * F2_BUF, ci + 1 < nk);
-      load_x(min(t0 + ci + 2, t1 - 1));  // (before the dZ2 pieces: a spill reload for these
-      __builtin_amdgcn_sched_barrier(0);  // addresses would otherwise wait for them)
-      load_dz(min(t0 + ci + 2, t1 - 1));
-      F2_STAMP(2);
-      phase_barrier();
-      F2_STAMP(3);
-    }
-  } else {
-    for (int ci = 0; ci < nk; ++ci) {
-      produce(sm + ((ci + 1) & 1) * F2_BUF, ci + 1 < nk);
-      load_x(min(t0 + ci + 2, t1 - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      load_dz(min(t0 + ci + 2, t1 - 1));
-      F2_STAMP(2);
-      phase_barrier();
-      F2_STAMP(3);
-      mfma_chunk(sm + (ci & 1) * F2_BUF);
-      F2_STAMP(1);
-      phase_barrier();
-      F2_STAMP(3);
-    }
-  }
-#undef F2_STAMP
-
-  float* out = N.part_w2 + (size_t)blockIdx.x * SF_W2_PSTRIDE;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        out[(size_t)(64 * wm + 32 * i + acc_row(q, l)) * HID + 128 * wn + 32 * j + r] = acc[i][j][q] * unscale;
-  // db2: sum over the 16 lanes c of the same n
-#pragma unroll
-  for (int j = 0; j < 8; ++j) db2[j] = row_sum16(db2[j]);
-  if (c == 0)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) N.part_b2[(size_t)blockIdx.x * HID + 32 * w + 16 * (j >> 2) + 4 * gq + (j & 3)] = db2[j];
-#ifdef RLKS_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  tph[4] = F2_NOW() - tq;
-  if (l == 0 && blockIdx.x < 128) {
-    unsigned long long* o = g_f2_stamps[blockIdx.y][blockIdx.x][w];
-    for (int i = 0; i < 5; ++i) o[i] = tph[i];
-    o[5] = ts0;
-  }
-#endif
-}
-
-// F2 with H1 in registers (round 6): dW2^T = H1^T dZ2 over the workgroup's rows, eight waves of 32
-// hidden units k x 256 outputs n (8 v_mfma_f32_32x32x16_f16 tiles, 128 accumulator registers, two
-// waves per SIMD).  Wave w's A operand is H1 of its own hidden units k = 32 w + (l & 31), taken from
-// its Z1 = Xa W1a^T accumulator as it stands: the accumulator's rows acc_row(8 s + j) are the K order
-// perm(s, h, j) in which k_sf_dw2's transposed reads deliver the dZ2 chunk, so that image is this
-// kernel's B operand unchanged.  No H1 image and no ping-pong between wave halves (k_sf_dw2's phases,
-// bound by their pairing): every wave issues its MFMAs of chunk c beside its own
-// production of chunk c + 1 (its share of the dZ2 image, its H1), one barrier per chunk.  Each wave
-// holds 4 consecutive k of one n per accumulator quad, so the partials are written in [k / 4][n][4]
-// order (16-byte stores, 512 contiguous bytes per half-wave); the reduce maps them back
-// (RedTask::kq).
-constexpr int F2R_ABUF = 2 * F2_APLANE;
-#ifndef F2R_DIAG
-#define F2R_DIAG 0  // (timing-only diagnostic builds, wrong gradients: 1 no partial stores, 2 no MFMAs, 3 no production)
-#endif  // halves per buffer: the dZ2 image's hi and lo planes
 template <int KD, int P>
 __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
   const SfNet& N = g.n[blockIdx.y];
@@ -1500,7 +1194,8 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
   if (!dcheck(t1 <= g.M / 32, DC_SGD_TILE, t1)) t0 = t1 = 0;
   const int nk = t1 - t0;
 
-  // F1a's X and dZ2 exponents of the workgroup's 16-row tiles -> LDS; E = min e_T (as k_sf_dw2)
+  // F1a's X and dZ2 exponents of the workgroup's 16-row tiles -> LDS (read per chunk from there, not by a
+  // global load among the prefetches); E = min e_T
   int* sEx = reinterpret_cast<int*>(sm + 2 * F2R_ABUF);
   int* sEd = sEx + F2_MAX_TILES;
   int emin = 120;
@@ -1520,7 +1215,8 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
   const float ssgn = tile_sign(blockIdx.x);  // odd splits: products on -H1, partial negated back
   const float unscale = ssgn * pow2(-14 - E);
 
-  // B fragments (k_sf_dw2's A reads): output block n = 32 ob + r, K order of k-step s as above
+  // B fragments (the transposed reads above): output block n = 32 ob + r; aq = this lane's quad within
+  // the 8-quad block, swizzled for rows 4 h + q (the rows + 8 of the second read flip bit 2 of the XOR)
   const int aq = (4 * ((l >> 4) & 1) + (l & 3)) ^ (2 * h);
   const int bbase = (4 * h + ((l & 15) >> 2)) * F2_AROW + 4 * aq;
   const int bbase8 = (4 * h + ((l & 15) >> 2) + 8) * F2_AROW + 4 * (aq ^ 4);
@@ -1544,7 +1240,8 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
       }
   };
 
-  // dZ2 pieces (k_sf_dw2's load_dz / store_dz: wave w moves n-step w of the chunk's two tiles)
+  // dZ2 pieces (the stores above): wave w moves n-step w of the chunk's two tiles; s0, s1 = 2^-e of the
+  // two tiles for db2 (0: a chunk redone past the end, not counted)
   const __amdgpu_buffer_rsrc_t dz_rsrc = __builtin_amdgcn_make_buffer_rsrc(N.dz2s, (short)0, 0x7fffffff, 0x00020000);
   const int dz_lane = 2 * (w * 1024 + l * 8);
   h8 dp[4];
@@ -1569,7 +1266,9 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
   };
 
   // H1 of the chunk for this wave's hidden units kh = 32 w + r: Z1 = Xa W1a^T on
-  // v_mfma_f32_32x32x8_f16 (as k_sf_dw2), tanh, split into the two k-steps' A fragments
+  // v_mfma_f32_32x32x8_f16 (K = 8 columns of Xa per MFMA), tanh, split into the two k-steps' A fragments
+  // (at KD = 32 the W1a fragments are reloaded at every production: kept for the whole kernel they
+  // make it spill)
   constexpr int KB = KD / 8;
   const int kh = 32 * w + r;
   h4 wh[KB], wl[KB];
@@ -1624,7 +1323,10 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
       split8v(x, hh[s], hl[s]);
     }
   };
-  auto barrier = [&]() {  // (k_sf_dw2's phase barrier: LDS stores drained, prefetches left in flight)
+  // barrier without __syncthreads()'s fence (s_waitcnt vmcnt(0) would wait for the prefetches in flight):
+  // the LDS stores need only lgkmcnt(0).  Scheduling barriers on both sides keep each chunk's VALU on
+  // its side.
+  auto barrier = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1661,9 +1363,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
       load_x(min(t0 + ci + 2, t1 - 1));
       __builtin_amdgcn_sched_barrier(0);
       load_dz(min(t0 + ci + 2, t1 - 1));
-#if F2R_DIAG != 2
       mfma_chunk(sm + (ci & 1) * F2R_ABUF, hh, hl);
-#endif
       barrier();
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -1673,20 +1373,14 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
     }
   } else
   for (int ci = 0; ci < nk; ++ci) {
-#if F2R_DIAG != 2
     mfma_chunk(sm + (ci & 1) * F2R_ABUF, hh, hl);
-#endif
     // chunk ci + 1 (past the end: the last chunk again, into the idle buffer, uncounted -- unconditional,
     // so that this production shares the MFMAs' basic block)
     const bool counted = ci + 1 < nk;
     const float s0 = counted ? pow2(-de.x) : 0.f, s1 = counted ? -pow2(-de.y) : 0.f;
     h8 nh[2], nl[2];
-#if F2R_DIAG != 3
     store_dz(sm + ((ci + 1) & 1) * F2R_ABUF, s0, s1);
     make_h1(nh, nl);
-#else
-    nh[0] = hh[1]; nh[1] = hh[0]; nl[0] = hl[1]; nl[1] = hl[0];
-#endif
     load_x(min(t0 + ci + 2, t1 - 1));
     __builtin_amdgcn_sched_barrier(0);
     load_dz(min(t0 + ci + 2, t1 - 1));
@@ -1706,11 +1400,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
     for (int t = 0; t < 4; ++t) {
       const v4f v = {acc[ob][4 * t] * unscale, acc[ob][4 * t + 1] * unscale, acc[ob][4 * t + 2] * unscale,
                      acc[ob][4 * t + 3] * unscale};
-#if F2R_DIAG != 1
       *reinterpret_cast<v4f*>(out + ((size_t)(8 * w + 2 * t + h) * HID + 32 * ob + r) * 4) = v;
-#else
-      if (v[0] == 1.2345f) out[0] = v[1];  // (keeps the accumulators live)
-#endif
     }
 #pragma unroll
   for (int j = 0; j < 8; ++j) db2[j] = row_sum16(db2[j]);
@@ -1869,75 +1559,57 @@ int launch_sf_prep(const SfPrepArgs& a, hipStream_t s) {
 }
 
 template <int A_, int KD, int P>
-static int launch_f1_net_p(SfArgs a, int net0, int nets, hipStream_t s, int halves) {
+static int launch_f1_net_p(SfArgs a, int net0, int nets, hipStream_t s, SfF1Form form) {
   constexpr int W = SF_F1_W;
   a.net0 = net0;
   const dim3 grid(a.M / (16 * W) * nets);  // (f1_net_group)
-  if (halves == SF_F1_FUSED) {  // one fused kernel
+  if (form == SF_F1_FUSED) {  // one fused kernel
     constexpr int WF = SF_F1F_W;
     launch_timed(KEV_F1A, k_sf_f1<A_, KD, WF, P>, dim3(a.M / (16 * WF) * nets), dim3(64 * WF), f1_lds_bytes<A_, KD, WF>(),
                  s, a);
     RLKS_LAUNCHED();
     return RLKS_OK;
   }
-  if (halves & 1) {  // pi's LDS (A_ >= 1) covers the value net's
+  if (form & SF_F1_A) {  // pi's LDS (A_ >= 1) covers the value net's
     launch_timed(KEV_F1A, k_sf_fwd<A_, KD, W, P>, grid, dim3(64 * W), f1a_lds_bytes<A_, KD, W>(), s, a);
     RLKS_LAUNCHED();
   }
-  if (halves & 2) {
+  if (form & SF_F1_B) {
     launch_timed(KEV_F1B, k_sf_bwd<KD, 3 * A_ + 1, W, P>, grid, dim3(64 * W), f1b_lds_bytes<KD>(), s, a);
     RLKS_LAUNCHED();
   }
   return RLKS_OK;
 }
 template <int A_, int KD>
-static int launch_f1_net(const SfArgs& a, int net0, int nets, hipStream_t s, int halves) {
-  return a.products == 1 ? launch_f1_net_p<A_, KD, 1>(a, net0, nets, s, halves)
-                         : launch_f1_net_p<A_, KD, 3>(a, net0, nets, s, halves);
+static int launch_f1_net(const SfArgs& a, int net0, int nets, hipStream_t s, SfF1Form form) {
+  return a.products == 1 ? launch_f1_net_p<A_, KD, 1>(a, net0, nets, s, form)
+                         : launch_f1_net_p<A_, KD, 3>(a, net0, nets, s, form);
 }
 
 // obs_dim = 3 x clusters: C = 2, 4, 8 -> D = 6, 12, 24 (D + 1 <= 8, 16, 32)
 int sf_kd(int D) { return D + 1 <= 16 ? 16 : 32; }
 
-int launch_sf_f1(const SfArgs& a, int net0, int nets, int A, hipStream_t s, int halves) {
+int launch_sf_f1(const SfArgs& a, int net0, int nets, int A, hipStream_t s, SfF1Form form) {
   RLKS_REQUIRE(a.M % SF_ROWS == 0, RLKS_ERR_ARG, "split-fp16 SGD step: rows must be a multiple of 256");
   RLKS_REQUIRE(a.D == 3 * A, RLKS_ERR_UNSUPPORTED, "split-fp16 SGD step expects obs_dim = 3 x n_actions");
   switch (A) {
-    case 2: return launch_f1_net<2, 16>(a, net0, nets, s, halves);
-    case 4: return launch_f1_net<4, 16>(a, net0, nets, s, halves);
-    case 8: return launch_f1_net<8, 32>(a, net0, nets, s, halves);
+    case 2: return launch_f1_net<2, 16>(a, net0, nets, s, form);
+    case 4: return launch_f1_net<4, 16>(a, net0, nets, s, form);
+    case 8: return launch_f1_net<8, 32>(a, net0, nets, s, form);
     default: return fail(RLKS_ERR_UNSUPPORTED, "split-fp16 head is built for 2, 4 or 8 actions");
   }
 }
 
-bool sf_f2_regs() {
-  const char* e = getenv("RLKS_F2_IMAGE");  // (read per call: tests switch it within a process)
-  return !(e && e[0] == '1');
-}
-
 int launch_sf_dw2(const SfArgs& a, int splits, hipStream_t s) {
   RLKS_REQUIRE(a.tiles_per_split <= F2_MAX_TILES / 2, RLKS_ERR_ARG, "split-fp16 F2: too many row chunks per split");
-  if (sf_f2_regs()) {
-    const size_t lds = (size_t)2 * F2R_ABUF * sizeof(_Float16) + 2 * F2_MAX_TILES * sizeof(int);  // 76 KB
-    const bool p1 = a.products == 1;
-    if (sf_kd(a.D) == 16) {
-      if (p1) launch_timed(KEV_F2, k_sf_dw2r<16, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-      else launch_timed(KEV_F2, k_sf_dw2r<16, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-    } else {
-      if (p1) launch_timed(KEV_F2, k_sf_dw2r<32, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-      else launch_timed(KEV_F2, k_sf_dw2r<32, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-    }
-    RLKS_LAUNCHED();
-    return RLKS_OK;
-  }
-  const size_t lds = (size_t)2 * F2_BUF * sizeof(_Float16) + 2 * F2_MAX_TILES * sizeof(int);  // 140 KB
+  const size_t lds = (size_t)2 * F2R_ABUF * sizeof(_Float16) + 2 * F2_MAX_TILES * sizeof(int);  // 76 KB
   const bool p1 = a.products == 1;
   if (sf_kd(a.D) == 16) {
-    if (p1) launch_timed(KEV_F2, k_sf_dw2<16, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-    else launch_timed(KEV_F2, k_sf_dw2<16, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
+    if (p1) launch_timed(KEV_F2, k_sf_dw2r<16, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
+    else launch_timed(KEV_F2, k_sf_dw2r<16, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
   } else {
-    if (p1) launch_timed(KEV_F2, k_sf_dw2<32, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
-    else launch_timed(KEV_F2, k_sf_dw2<32, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
+    if (p1) launch_timed(KEV_F2, k_sf_dw2r<32, 1>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
+    else launch_timed(KEV_F2, k_sf_dw2r<32, 3>, dim3(splits, 2), dim3(F2_THREADS), lds, s, a);
   }
   RLKS_LAUNCHED();
   return RLKS_OK;

@@ -242,8 +242,8 @@ __global__ void k_wide_stats(const float* __restrict__ ps_pi, const float* __res
 // fused rollout kernels): action and its log-probability
 __global__ void k_wide_sample(EnvView v, const float* __restrict__ logits, int A, int explore,
                               int32_t* __restrict__ actions, float* __restrict__ logp) {
-  const int m = v.lane0 + blockIdx.x * blockDim.x + threadIdx.x;  // (a lane range: node_rollout's halves)
-  if (m >= v.lane_end) return;
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= v.N) return;
   const float* lg = logits + (size_t)m * A;
   float mx = lg[0];
   int amax = 0;
@@ -583,7 +583,7 @@ int forward_net(const rlks_mlp_desc* d, const Net& P, const WideNet& n, const fl
     RLKS_LAUNCHED();
     return RLKS_OK;
   }
-  if (An <= 64 && H % (16 * PH_KU) == 0 && !getenv("RLKS_WIDE_HEAD_GEMM")) {  // (RLKS_WIDE_HEAD_GEMM: the generic GEMM, A/B)
+  if (An <= 64 && H % (16 * PH_KU) == 0) {  // the streamed head; other shapes: the generic GEMM
     if (An <= 32)
       hipLaunchKernelGGL(k_wide_phead<1>, dim3(cdiv(M, 128)), dim3(256), 0, s, n.h2, P.w3, P.b3, sl + SL_W3, n.out, M, H, An);
     else
@@ -710,7 +710,7 @@ int wide_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* pa
 
 int launch_sample(const EnvView& v, const float* logits, int A, int explore, int32_t* actions, float* logp,
                   hipStream_t s) {
-  hipLaunchKernelGGL(k_wide_sample, dim3(cdiv(v.lane_end - v.lane0, 256)), dim3(256), 0, s, v, logits, A, explore,
+  hipLaunchKernelGGL(k_wide_sample, dim3(cdiv(v.N, 256)), dim3(256), 0, s, v, logits, A, explore,
                      actions, logp);
   RLKS_LAUNCHED();
   return RLKS_OK;

@@ -202,3 +202,21 @@ def test_reporting_window_is_bounded_by_the_episode_log():
         PPOConfig().reporting(metrics_num_episodes_for_smoothing=_lib.RLKS_EPLOG_CAP + 1)
     c = PPOConfig()
     assert c.checkpoint_env_state is None  # auto: table envs yes, node-level envs no
+
+
+def test_f1_form_switches_are_on_only_at_1(monkeypatch):
+    """rlks_sf_f1_fused (a host query): the fused F1 by default up to 4 actions; RLKS_F1_SPLIT=1 /
+    RLKS_F1_FUSED=1 force either form, and a value that does not start with 1 is the same as unset"""
+    from rlks import _lib
+
+    def fused():
+        return tuple(_lib.lib().rlks_sf_f1_fused(C.byref(_lib.MlpDesc(3 * A, 256, A, _lib.RLKS_PRECISION_SF16)))
+                     for A in (2, 8))
+
+    for env, want in [({}, (1, 0)), ({"RLKS_F1_SPLIT": "1"}, (0, 0)), ({"RLKS_F1_FUSED": "1"}, (1, 1)),
+                      ({"RLKS_F1_SPLIT": "0"}, (1, 0)), ({"RLKS_F1_FUSED": "0"}, (1, 0))]:
+        for k in ("RLKS_F1_SPLIT", "RLKS_F1_FUSED"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        assert fused() == want, env

@@ -83,7 +83,8 @@ def fwd_report(lib, tiles):
 
 
 def f2_report(lib):
-    """F2 (k_sf_dw2) per-wave phase cycles summed over its chunks (waves 0-7 of each workgroup)"""
+    """F2 per-wave phase cycles summed over its chunks (waves 0-7 of each workgroup).  The stamps were taken by
+    the rounds 3-5 kernel k_sf_dw2 (last in commit 61b17e2); k_sf_dw2r takes none yet, so the array reads zero"""
     st = np.zeros((2, 128, 16, 6), np.uint64)
     assert lib.rlks_dbg_f2_stamps(st.ctypes.data_as(C.c_void_p)) == 0
     names = ["prologue", "MFMA issue", "production", "barrier waits", "epilogue"]
