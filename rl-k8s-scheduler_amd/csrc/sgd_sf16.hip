@@ -412,9 +412,15 @@ __device__ unsigned long long g_fa_stamps[2][8192][8];
   if (l == 0 && tile < 8192)                                                                        \
   g_fa_stamps[NET][tile][7] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |       \
                               ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32)
+// F1b (f1b_body: k_sf_bwd, or the second half of k_sf_f1) the same way: 0 entry, 1 prologue landed,
+// 2 dH1 loop done, 3 Z1 recompute + dZ1 done, 4 Xa^T fragment ready, 5 dW1 products + flush done
+__device__ unsigned long long g_fb_stamps[2][8192][8];
+#define FB_STAMP(i) \
+  if (l == 0 && tile < 8192) g_fb_stamps[NET][tile][i] = __builtin_amdgcn_s_memtime()
 #else
 #define FA_STAMP(i)
 #define FA_HWID()
+#define FB_STAMP(i)
 #endif
 
 // ----------------------------------------------------------------------------- F1 (16-row tiles)
@@ -484,6 +490,46 @@ __device__ __forceinline__ void hc_frag(const _Float16* buf, int j, int c, int g
   const int off = (16 * j + c) * 32 + 8 * (g ^ sw16(c));
   fh = *reinterpret_cast<const h8*>(buf + off);
   fl = *reinterpret_cast<const h8*>(buf + H16 + off);
+}
+
+typedef __fp16 hf4_t __attribute__((vector_size(8)));
+// ds_read_b64_tr_b16 (T10): per 16-lane group, 4 rows x 16 columns of 16-bit elements, lane i of
+// the group gets column i (row q in element q); EXEC must be all ones
+__device__ __forceinline__ h4 tr_read(const _Float16* p) {
+  const hf4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hf4_t*)(p));
+  return __builtin_bit_cast(h4, v);
+}
+
+// Fused F1 (k_sf_f1): the tile's split Xa fragment stays in LDS from F1a to F1b, one image per wave:
+// [hi, lo][16 rows][XROW halves], lane (g, c) owns the 16-byte piece g of row c (the pieces past KD hold
+// the fragment's zeros, so every lane stores and loads its own piece unconditionally).  F1b reads the
+// Z1 recompute's fragment back as it stands and the dW1 product's Xa^T operand (rows d = 16 dt + c,
+// columns m = 4g + j) by one transposed read per plane and d-tile, instead of loading the X rows
+// again and redoing the selects, the wave max and both splits.
+constexpr int F1_EP_BYTES = 65536;  // fused F1b at KD = 16: dW1 epilogue slots of 4 k-tiles x 16 waves (f1b_body)
+constexpr int XROW = 32;
+constexpr int XIMG = 2 * 16 * XROW;  // halves per wave
+__device__ __forceinline__ void xs_store(_Float16* sX, int c, int g, h8 xh, h8 xl) {
+  *reinterpret_cast<h8*>(sX + c * XROW + 8 * g) = xh;
+  *reinterpret_cast<h8*>(sX + 16 * XROW + c * XROW + 8 * g) = xl;
+}
+__device__ __forceinline__ void xs_frag(const _Float16* sX, int c, int g, h8& xh, h8& xl) {
+  xh = *reinterpret_cast<const h8*>(sX + c * XROW + 8 * g);
+  xl = *reinterpret_cast<const h8*>(sX + 16 * XROW + c * XROW + 8 * g);
+}
+// Xa^T of d-tile dt: lane 4q + p of a 16-lane group addresses row 4g + q, columns 16 dt + 4p .. + 3 and
+// receives column 16 dt + c of rows 4g + j.  F1a split the tile times its sign; the dW1 product takes
+// Xa unsigned (u1 carries the sign), so odd tiles flip the sign bits back (flip = 0x80008000 or 0).
+// A zero half may come out as -0 where the element-wise split gave +0: as an MFMA operand it adds
+// nothing either way and the accumulators start from +0, so the products' bits are the same.
+__device__ __forceinline__ void xs_frag_t(const _Float16* sX, int dt, int c, int g, unsigned flip, h4& th, h4& tl) {
+  using v2u = __attribute__((ext_vector_type(2))) unsigned;
+  const _Float16* p = sX + (4 * g + (c >> 2)) * XROW + 16 * dt + 4 * (c & 3);
+  v2u a = __builtin_bit_cast(v2u, tr_read(p)), b = __builtin_bit_cast(v2u, tr_read(p + 16 * XROW));
+  a ^= flip;
+  b ^= flip;
+  th = __builtin_bit_cast(h4, a);
+  tl = __builtin_bit_cast(h4, b);
 }
 
 // W1a = [W1 | b1] (hi, lo) in LDS: [2][HID k][KD] halves; at KD = 32 the 16-byte pieces of a row
@@ -614,8 +660,14 @@ constexpr int f1b_lds_bytes() {
 //   dW3[A-1] = -sum_{a < A-1} dW3[a]
 // which is the same loss and gradient with A - 1 head rows instead of A (at 2 actions: half of the
 // head, of dZ2's products and of the dW3 reduce-scatter, the epilogue's largest part).  AH: head rows.
-template <int A_, int NET, int KD, int W, int P>
-__device__ __forceinline__ int f1a_body(const SfArgs& g, int grp) {
+// the lane's dZ2 fragment of n-step 0 as F1a split it: k_sf_f1 hands it to F1b in registers, so that
+// F1b's prologue waits for no load (it reads the later n-steps back from the dz2s it shares with F2)
+struct DzFrag {
+  h8 h, l;
+};
+// XOFF >= 0 (k_sf_f1): the byte offset in the dynamic LDS of the waves' Xa images kept for F1b (xs_store)
+template <int A_, int NET, int KD, int W, int P, int XOFF = -1>
+__device__ __forceinline__ int2 f1a_body(const SfArgs& g, int grp, DzFrag* dz0 = nullptr) {
   constexpr int NTHR = 64 * W;
   constexpr int AH = NET == 0 ? A_ - 1 : 1;
   const SfNet& N = g.n[NET];
@@ -669,6 +721,7 @@ __device__ __forceinline__ int f1a_body(const SfArgs& g, int grp) {
   h8 xh, xl;
   const float sgn = tile_sign(tile);
   const int ex = x_split(xv, xh, xl, sgn);
+  if constexpr (XOFF >= 0) xs_store(reinterpret_cast<_Float16*>(lds) + XOFF / 2 + w * XIMG, c, gq, xh, xl);
   if ((NET == 0 || g.net0 == 1) && 8 * gq < KD) {  // the rows' Xa split for F2: by the policy net (both
                                                     // nets split the same rows alike), or the value net alone
     _Float16* xo = g.xsp + (size_t)(row0 + c) * KD + 8 * gq;
@@ -724,6 +777,11 @@ __device__ __forceinline__ int f1a_body(const SfArgs& g, int grp) {
     if (t == 0) FA_STAMP(2);
   }
   FA_STAMP(3);
+  // k_sf_f1: F1b's first W2^T half-chunk goes out now, into a buffer of its own behind the Xa images
+  // (nothing of either phase aliases it), and lands under this epilogue; the barrier that ends F1a
+  // waits for it, so F1b's first step starts from a landed buffer instead of a memory round trip
+  if constexpr (XOFF >= 0)
+    hc_dma<W>(N.w2th, N.w2tl, 0, 0, reinterpret_cast<_Float16*>(lds) + XOFF / 2 + W * XIMG, w, l);
 
   // ---- H2^T = tanh(Z2^T + b2) (lane: rows n = 16 nt + 4g + i of column m = c); head
   // out[a] = b3 + sum_n W3[a][n] H2[n] (partial over the lane's 64 n, then over the four rows)
@@ -844,6 +902,11 @@ __device__ __forceinline__ int f1a_body(const SfArgs& g, int grp) {
       split8v(x, hi, lo);
       *reinterpret_cast<h8*>(dst + st * 1024) = hi;
       *reinterpret_cast<h8*>(dst + st * 1024 + 512) = lo;
+      if constexpr (XOFF >= 0 && P == 3)  // (P == 1, the fp16 throughput mode: one register too many, F1b loads it)
+        if (st == 0) {
+          dz0->h = hi;
+          dz0->l = lo;
+        }
     }
   }
   if (l == 0) {
@@ -885,7 +948,7 @@ __device__ __forceinline__ int f1a_body(const SfArgs& g, int grp) {
       vf_b3_part(vx, g.co.vf_loss_coeff, load_dyn(g).inv_count, N.part_b3 + (size_t)blk * 2);
     }
   }
-  return edz;  // (wave-uniform: the fused F1 hands it to f1b_body in a register)
+  return make_int2(edz, __builtin_amdgcn_readfirstlane(ex));  // (wave-uniform: the fused F1 hands them to f1b_body in registers)
 }
 
 // workgroup -> (net, tile group) for F1a / F1b launched as one row of G x nets workgroups.  Both
@@ -925,12 +988,18 @@ bool sf_f1_fused(int A) {
 // FUSED (k_sf_f1: right after f1a_body in the same workgroup): the tile's dZ2 exponent arrives in a
 // register (edz_in), and the W1a planes F1a staged are still in LDS when its epilogue slots stopped
 // short of them (W1_KEPT)
-template <int NET, int KD, int ND, int W, int P, bool FUSED = false, bool W1_KEPT = false>
-__device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 0) {  // ND = obs_dim + 1 (rows d of dW1a^T)
+template <int NET, int KD, int ND, int W, int P, bool FUSED = false, bool W1_KEPT = false, int XOFF = -1>
+__device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 0, int ex_in = 0,
+                                         const DzFrag* dz0 = nullptr) {  // ND = obs_dim + 1 (rows d of dW1a^T)
   constexpr int NTHR = 64 * W;
   constexpr int DT = KD / 16;                      // 16-row d-tiles of dW1a^T
   constexpr int SLOT = W * 16 * 16 * DT;           // floats per k-tile: [W][16 k][16 DT d]
-  constexpr int KPR = (4 * H16 * 2 / 4) / SLOT;    // k-tiles per flush round (the half-chunk buffers)
+  // k-tiles per flush round: what the half-chunk buffers hold; FUSED at KD = 16: four (F1_EP_BYTES: the
+  // slots run on over the W1a planes and F1a's head constants, all dead by then), so that the 16 k-tiles
+  // take 4 flush rounds and 7 barriers instead of 8 and 15.  Every element is summed over the waves in
+  // the same order whatever the round size.
+  constexpr bool EP4 = FUSED && KD == 16;
+  constexpr int KPR = EP4 ? F1_EP_BYTES / 4 / SLOT : (4 * H16 * 2 / 4) / SLOT;
   static_assert(KPR >= 1 && 16 % KPR == 0, "dW1 epilogue slots");
   const SfNet& N = g.n[NET];
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -949,13 +1018,24 @@ __device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 
   const int row0 = tile * 16, blk = grp;
   const int D = g.D, stride = g.x_stride;
 
-  hc_dma<W>(N.w2th, N.w2tl, 0, 0, sCh, w, l);
+  FB_STAMP(0);
+  // (k_sf_f1 with the Xa images: F1a sent the first half-chunk to the buffer behind them; step 0 reads it there)
+  const _Float16* sPre = XOFF >= 0 ? reinterpret_cast<const _Float16*>(lds) + XOFF / 2 + W * XIMG : sCh;
+  if constexpr (XOFF < 0) hc_dma<W>(N.w2th, N.w2tl, 0, 0, sCh, w, l);
   if constexpr (!W1_KEPT) w1_stage<KD, NTHR>(N, sW1, tid);
   const int edz = FUSED ? edz_in : N.tile_edz[tile];
   const _Float16* dzp = N.dz2s + (size_t)tile * (16 * HID * 2) + l * 8;  // split by F1a at 2^edz
-  h8 dh = *reinterpret_cast<const h8*>(dzp), dl = *reinterpret_cast<const h8*>(dzp + 512);
+  h8 dh, dl;
+  if constexpr (XOFF >= 0 && P == 3) {
+    dh = dz0->h;
+    dl = dz0->l;
+  } else {
+    dh = *reinterpret_cast<const h8*>(dzp);
+    dl = *reinterpret_cast<const h8*>(dzp + 512);
+  }
   vm_drain();
   __syncthreads();
+  FB_STAMP(1);
 
   // ---- dH1 = dZ2 W2: 16 steps (n-step s, k-half ph) of 8 k-tiles x 3 MFMAs; the (pre-split) dZ2
   // fragment of n-step s taken at its first step and the next one loaded
@@ -976,7 +1056,7 @@ __device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 
           dl = *reinterpret_cast<const h8*>(dzp + (s + 1) * 1024 + 512);
         }
       }
-      const _Float16* buf = sCh + ph * 2 * H16;
+      const _Float16* buf = (ph == 0 && s == 0) ? sPre : sCh + ph * 2 * H16;
       h8 ch, cl;
       hc_frag(buf, 0, c, gq, ch, cl);
 #pragma unroll
@@ -998,9 +1078,18 @@ __device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 
   // at 2^(e_dz + e_w2 - 23) from the bound |dH1 2^(e_dz + e_w2)| <= 256 2^15 2^15: typical tiles then
   // sat 2^8-2^12 below it and their lo halves fell into fp16 subnormals, dW1 / db1 ~5x less accurate
   // per element than fp32); then dW1a^T = Xa^T dZ1 per k-tile
+  FB_STAMP(2);
   h8 xh, xl;
   const float sgn = tile_sign(tile);
-  const int ex = x_frag(g, row0, c, gq, xh, xl, sgn);
+  constexpr bool XKEPT = XOFF >= 0;  // (k_sf_f1 up to 4 actions: F1a left the tile's Xa image in LDS)
+  const _Float16* sX = reinterpret_cast<const _Float16*>(lds) + (XKEPT ? XOFF / 2 : 0) + w * XIMG;
+  int ex;
+  if constexpr (XKEPT) {  // F1a's fragment and exponent of the same tile
+    xs_frag(sX, c, gq, xh, xl);
+    ex = ex_in;
+  } else {
+    ex = x_frag(g, row0, c, gq, xh, xl, sgn);
+  }
   const float sx = pow2(ex), k_z1 = sgn * N.sc[1] / sx * SF_2LOG2E;
   // 1 - H1^2 = 4 r (1 - r): the 4 joins the unscaling power of two
   float zmx = 0.f;
@@ -1017,30 +1106,51 @@ __device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 
       zmx = fmaxf(zmx, fabsf(acc[kt][i]));
     }
   }
+  FB_STAMP(3);
   const int ez = sf_exp(wave_max(zmx));
   const float sz1 = pow2(ez), u1 = sgn * pow2(2 - ex - edz - (int)N.sc[5] - ez);  // (sgn: F1a's tile sign)
   h4 xth[DT], xtl[DT];  // Xa^T (16x16x16 A operand): rows d = 16 dt + c, columns m = 4g + j
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
+  for (int dt = 0; dt < DT; ++dt) {
+    if constexpr (XKEPT) {
+      xs_frag_t(sX, dt, c, gq, (tile & 1) ? 0x80008000u : 0u, xth[dt], xtl[dt]);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      _Float16 a, b;
-      split1(xa_elem(g.x + (size_t)(row0 + 4 * gq + j) * stride, 16 * dt + c, D) * sx, a, b);
-      xth[dt][j] = a;
-      xtl[dt][j] = b;
+      for (int j = 0; j < 4; ++j) {
+        _Float16 a, b;
+        split1(xa_elem(g.x + (size_t)(row0 + 4 * gq + j) * stride, 16 * dt + c, D) * sx, a, b);
+        xth[dt][j] = a;
+        xtl[dt][j] = b;
+      }
     }
+  }
   // dZ1's lo half carried at 2^11 (its own accumulator, unscaled at the end): an element far below
   // the tile's max keeps a normal fp16 lo (a plain lo half turns subnormal 2^18 below the max)
   const float u1l = u1 * (1.f / 2048.f);
+  FB_STAMP(4);
+  if constexpr (EP4) __syncthreads();  // every wave is done with the W1a planes (Z1 above) before slots land on them
 #pragma unroll
   for (int kt = 0; kt < 16; ++kt) {
     h4 zh, zl;
+    if constexpr (FUSED && KD == 16) {  // (the fused kernel's default range; at 8 actions it is at the register budget as it stands)
+      // the same bits in fewer instructions: hi = f16(x) (v_cvt_pk_f16_f32 for a pair), lo = f16(2048 x -
+      // 2048 hi) as one v_fma_mix{lo,hi}_f16 (its fp32 result 2048 (x - hi) is exact, so it rounds once,
+      // like the cvt / cvt back / sub / mul / cvt below)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float x = acc[kt][i] * sz1;
-      const _Float16 a = (_Float16)x;
-      zh[i] = a;
-      zl[i] = (_Float16)((x - (float)a) * 2048.f);
+      for (int i = 0; i < 4; ++i) {
+        const float x = acc[kt][i] * sz1, X = x * 2048.f;
+        const _Float16 a = (_Float16)x;
+        zh[i] = a;
+        zl[i] = (_Float16)fmaf(-(float)a, 2048.f, X);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float x = acc[kt][i] * sz1;
+        const _Float16 a = (_Float16)x;
+        zh[i] = a;
+        zl[i] = (_Float16)((x - (float)a) * 2048.f);
+      }
     }
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -1070,6 +1180,7 @@ __device__ __forceinline__ void f1b_body(const SfArgs& g, int grp, int edz_in = 
       if (kt < 15) __syncthreads();
     }
   }
+  FB_STAMP(5);
 }
 
 template <int KD, int ND, int W, int P>
@@ -1087,30 +1198,45 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // different phases a few policy tiles a step came out different from run to run (cause not isolated).
 // Measured no faster than the two kernels on round 6's first trees (126-128 µs against 126 µs for the
 // pair at c4); faster end to end with k_sf_dw2r and the no-SLP build (profiles/r06_fusedab).
+// Up to 4 actions (KD = 16; DESIGN.md §16, profiles/r08_f1) F1a also leaves F1b, inside the workgroup:
+// the tile's split Xa fragment in LDS (xs_store: F1b neither loads the X rows nor splits them again, and
+// takes Xa^T by transposed LDS reads), the first W2^T half-chunk (sent by LDS-DMA at the start of F1a's
+// epilogue into a buffer nothing aliases) and the first dZ2 fragment in registers, so F1b's prologue
+// waits for no memory round trip; F1b splits dZ1 with v_fma_mix and flushes dW1 four k-tiles a round.
+// LDS: [phase regions, 64 KB at least][Xa images W x 2 KB][W2^T half-chunk 16 KB].  All of it moves the
+// same bits: the gradient is byte-identical to the kernel without them.
 template <int A_, int KD, int W>
 constexpr bool f1_w1_kept() {  // F1a's epilogue slots end before the W1a planes (sW1 = 4 H16 halves in)
   return W * (A_ - 1 > 1 ? A_ - 1 : 1) * HID * 4 + W * (A_ + 4) * 4 <= 4 * H16 * 2;
 }
 template <int A_, int KD, int W>
 constexpr int f1_lds_bytes() {
-  return f1a_lds_bytes<A_, KD, W>() > f1b_lds_bytes<KD>() ? f1a_lds_bytes<A_, KD, W>() : f1b_lds_bytes<KD>();
+  constexpr int ab = f1a_lds_bytes<A_, KD, W>() > f1b_lds_bytes<KD>() ? f1a_lds_bytes<A_, KD, W>() : f1b_lds_bytes<KD>();
+  constexpr int ep = KD == 16 ? F1_EP_BYTES : 0;  // F1b's dW1 slots of the fused kernel (f1b_body, EP4)
+  return ab > ep ? ab : ep;
 }
+template <int A_>
+constexpr bool f1_x_kept() { return A_ <= 4; }
 template <int A_, int KD, int W, int P>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_sf_f1(SfArgs g) {
   const int2 ng = f1_net_group<W, (A_ <= 4)>(g);
   // F1b's loads of the X rows are the ones F1a made: an opaque copy of the row pointer keeps the
   // compiler from carrying F1a's values across the epilogue in registers (which spilled)
   SfArgs g2 = g;
+  // the Xa images (xs_store) follow both nets' phase regions; up to 4 actions (at 8, forced by
+  // RLKS_F1_FUSED=1, F1a's epilogue slots leave no room for them and F1b loads the X rows again)
+  constexpr int XOFF = f1_x_kept<A_>() ? f1_lds_bytes<A_, KD, W>() : -1;
+  DzFrag dz0;
   if (ng.x + g.net0 == 0) {
-    const int edz = f1a_body<A_, 0, KD, W, P>(g, ng.y);
+    const int2 e = f1a_body<A_, 0, KD, W, P, XOFF>(g, ng.y, &dz0);
     __syncthreads();  // epilogue slots read; the dZ2 stores complete (the fence waits for them)
     asm volatile("" : "+s"(g2.x));
-    f1b_body<0, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<A_, KD, W>()>(g2, ng.y, edz);
+    f1b_body<0, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<A_, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, &dz0);
   } else {
-    const int edz = f1a_body<1, 1, KD, W, P>(g, ng.y);
+    const int2 e = f1a_body<1, 1, KD, W, P, XOFF>(g, ng.y, &dz0);
     __syncthreads();
     asm volatile("" : "+s"(g2.x));
-    f1b_body<1, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<1, KD, W>()>(g2, ng.y, edz);
+    f1b_body<1, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<1, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, &dz0);
   }
 }
 
@@ -1164,13 +1290,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // wave) spilled at the 128-register budget, each spill reload waiting for the prefetches in flight
 // (vmcnt counts in issue order).  This kernel needs no H1 image and no pairing: same box, c4 F2
 // 55.1-55.2 -> 49.9-50.2 us, c3 78.0 -> 75.8 us (profiles/r06_f2regs).
-typedef __fp16 hf4_t __attribute__((vector_size(8)));
-// ds_read_b64_tr_b16 (T10): per 16-lane group, 4 rows x 16 columns of 16-bit elements, lane i of
-// the group gets column i (row q in element q); EXEC must be all ones
-__device__ __forceinline__ h4 tr_read(const _Float16* p) {
-  const hf4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hf4_t*)(p));
-  return __builtin_bit_cast(h4, v);
-}
 #ifdef RLKS_STAMPS
 // diagnostic build only (tools/stamps.py): F2 phase cycles of lane 0 of every wave,
 // [net][split][wave][prologue, MFMA issue, production, barrier waits, epilogue, start]
@@ -1540,6 +1659,9 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 extern "C" int rlks_dbg_fa_stamps(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fa_stamps), sizeof(g_fa_stamps)) == hipSuccess ? 0 : 1;
 }
+extern "C" int rlks_dbg_fb_stamps(unsigned long long* host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fb_stamps), sizeof(g_fb_stamps)) == hipSuccess ? 0 : 1;
+}
 extern "C" int rlks_dbg_f2_stamps(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_f2_stamps), sizeof(g_f2_stamps)) == hipSuccess ? 0 : 1;
 }
@@ -1565,8 +1687,8 @@ static int launch_f1_net_p(SfArgs a, int net0, int nets, hipStream_t s, SfF1Form
   const dim3 grid(a.M / (16 * W) * nets);  // (f1_net_group)
   if (form == SF_F1_FUSED) {  // one fused kernel
     constexpr int WF = SF_F1F_W;
-    launch_timed(KEV_F1A, k_sf_f1<A_, KD, WF, P>, dim3(a.M / (16 * WF) * nets), dim3(64 * WF), f1_lds_bytes<A_, KD, WF>(),
-                 s, a);
+    launch_timed(KEV_F1A, k_sf_f1<A_, KD, WF, P>, dim3(a.M / (16 * WF) * nets), dim3(64 * WF),
+                 f1_lds_bytes<A_, KD, WF>() + (f1_x_kept<A_>() ? WF * XIMG * 2 + 2 * H16 * 2 : 0), s, a);
     RLKS_LAUNCHED();
     return RLKS_OK;
   }

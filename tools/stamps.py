@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timing of the split-fp16 F1a (k_sf_fwd) and F2 (k_sf_dw2) kernels from in-kernel s_memtime stamps (diagnostic build).
+"""Phase timing of the split-fp16 F1a / F1b (k_sf_fwd / k_sf_bwd, or the fused k_sf_f1) and F2 (k_sf_dw2) kernels from in-kernel s_memtime stamps (diagnostic build).
 
   make -C rl-k8s-scheduler_amd/csrc stamps
   RLKS_LIB=rl-k8s-scheduler_amd/rlks/librlks_stamps.so python tools/stamps.py
@@ -82,6 +82,30 @@ def fwd_report(lib, tiles):
     print("first 12 waves (start, end, simd key):", [(int(start[i]), int(end[i]), int(k[i])) for i in order[:12]])
 
 
+def bwd_report(lib, tiles):
+    """F1b (f1b_body: k_sf_bwd, or the second half of the fused k_sf_f1) phases per wave; with the fused
+    kernel also the gap between F1a's last stamp and F1b's first, and a wave's whole F1 lifetime"""
+    st = np.zeros((2, 8192, 8), np.uint64)
+    assert lib.rlks_dbg_fb_stamps(st.ctypes.data_as(C.c_void_p)) == 0
+    fa = np.zeros((2, 8192, 8), np.uint64)
+    assert lib.rlks_dbg_fa_stamps(fa.ctypes.data_as(C.c_void_p)) == 0
+    names = ["prologue", "dH1 loop", "Z1 + dZ1", "dZ1 exponent + Xa^T", "dW1 products + flush"]
+    for net in range(2):
+        s = st[net, :tiles, :6].astype(np.int64)
+        a = fa[net, :tiles, :7].astype(np.int64)
+        dt = np.diff(s, axis=1)
+        print(f"F1b net {net}: wave lifetime median {np.median(s[:, 5] - s[:, 0]):.0f} cyc")
+        for i, n in enumerate(names):
+            print(f"  {n:22s} median {np.median(dt[:, i]):8.0f}  p90 {np.percentile(dt[:, i], 90):8.0f}")
+        gap = s[:, 0] - a[:, 6]
+        print(f"  F1a's last stamp -> F1b entry median {np.median(gap):.0f}; F1a entry -> F1b end median "
+              f"{np.median(s[:, 5] - a[:, 0]):.0f} (meaningful for the fused kernel only)")
+    # workgroup turnover of the fused kernel: per net, the tiles of one CU slot in start order
+    t_all = np.concatenate([fa[n, :tiles, 0].astype(np.int64) for n in range(2)])
+    e_all = np.concatenate([st[n, :tiles, 5].astype(np.int64) for n in range(2)])
+    print(f"kernel span (first F1a entry -> last F1b end) {e_all.max() - t_all.min():.0f} cyc")
+
+
 def f2_report(lib):
     """F2 per-wave phase cycles summed over its chunks (waves 0-7 of each workgroup).  The stamps were taken by
     the rounds 3-5 kernel k_sf_dw2 (last in commit 61b17e2); k_sf_dw2r takes none yet, so the array reads zero"""
@@ -129,7 +153,8 @@ def main():
         _lib.call("rlks_ppo_grad", C.byref(p.desc), C.byref(co), p.flat.data_ptr(), dyn.data_ptr(), mbt.data_ptr(),
                   rows, grad.data_ptr(), None, ws.data_ptr(), ws.numel(), None)
     torch.cuda.synchronize()
-    fwd_report(_lib.lib(), rows // 16)  # F1a (k_sf_fwd) phases, one wave per 16-row tile
+    fwd_report(_lib.lib(), rows // 16)  # F1a (k_sf_fwd / k_sf_f1) phases, one wave per 16-row tile
+    bwd_report(_lib.lib(), rows // 16)  # F1b (k_sf_bwd / k_sf_f1)
     f2_report(_lib.lib())
 
 if __name__ == "__main__":
