@@ -249,7 +249,8 @@ int rlks_ppo_gather_packed(const rlks_mlp_desc* desc, const float* packed_dev, i
 
 /* Gradient of the RLlib PPO loss (mean over `rows`*world rows via dyn[INV_COUNT]) w.r.t. the
  * flat parameters -> grad_dev (padded_count floats).  stats_dev (double[RLKS_STAT_SIZE]) gets
- * the sums for reporting and the KL update.  workspace from rlks_ppo_workspace_bytes. */
+ * the sums for reporting and the KL update.  workspace from rlks_ppo_workspace_bytes (the gradient's
+ * scratch for `rows` rows, then the gradient-clipping entry points' norm scratch). */
 int rlks_ppo_workspace_bytes(const rlks_mlp_desc* desc, int rows, int64_t* bytes);
 /* Diagnostics (tools/f1b_isolate.py): the split-fp16 step's dZ2 hand-off inside `workspace` for `rows`
  * minibatch rows: out[net] = dZ2 planes ([rows / 16 tiles][8][hi, lo][64][8] fp16, sgd_sf16.hip F1a),
@@ -359,6 +360,43 @@ int rlks_ppo_grad_step_part(const rlks_mlp_desc* desc, const rlks_ppo_coeffs* co
 int rlks_ppo_adam_apply(const rlks_mlp_desc* desc, float* params_dev, const float* grad_dev, float* adam_m_dev,
                         float* adam_v_dev, int64_t n_params, float lr, float beta1, float beta2, float eps, int step,
                         void* workspace, int64_t ws_bytes, int rows, void* stream);
+
+/* ---- global-norm gradient clipping (PPOConfig.training(grad_clip=c), grad_clip_by "global_norm").
+ * Restates RLlib's old-API-stack torch policy (ray/rllib/utils/torch_utils.py apply_grad_clipping,
+ * one optimizer over every parameter of both nets) and torch.nn.utils.clip_grad_norm_ (norm_type 2);
+ * both are third-party and absent from the reference tree, the arithmetic is pinned by
+ * tests/clip_ref.py.  Per SGD step, over the true elements of the 12 tensors (layout padding is never
+ * read):
+ *   S = sum g^2 in f64 (squares of fp32 values are exact), one fixed summation order that does not
+ *       depend on the kernel that produced g;  norm = sqrt(S);
+ *   coef = (float) fmin(1.0, (double) grad_clip / (norm + 1e-6));  g <- g * coef (fp32, round to nearest);
+ *   Adam (rlks_adam_step's arithmetic) on the clipped g, which grad_dev holds afterwards, as torch
+ *   leaves p.grad.  stats_dev[RLKS_STAT_GRAD_GNORM] = norm (before clipping).
+ * grad_clip must be finite and > 0 (RLKS_ERR_ARG).  The workspace is the step's own,
+ * rlks_ppo_workspace_bytes(desc, rows) bytes: the norm's scratch lies behind the gradient's. */
+
+/* The norm alone (a test surface, like rlks_absmax): *norm_dev (double) = the global norm of the flat
+ * gradient grad_dev (n_params = padded_count).  workspace: any scratch of at least
+ * rlks_ppo_workspace_bytes(desc, any valid rows) bytes, overwritten from its start -- not the
+ * workspace of a run between two of its SGD steps. */
+int rlks_grad_global_norm(const rlks_mlp_desc* desc, const float* grad_dev, int64_t n_params, double* norm_dev,
+                          void* workspace, int64_t ws_bytes, void* stream);
+/* rlks_ppo_sgd_step_next with clipping (next may be NULL).  Split-fp16: the gradient launches of
+ * rlks_ppo_grad_step_next, whose reduce also leaves one norm partial per block, the norm, then the
+ * clipped Adam pass of rlks_ppo_adam_apply_clip; other precisions: rlks_ppo_grad, the norm, Adam. */
+int rlks_ppo_sgd_step_clip(const rlks_mlp_desc* desc, const rlks_ppo_coeffs* coeffs, float* params_dev,
+                           const float* dyn_dev, const float* mb_dev, int rows, float* grad_dev, double* stats_dev,
+                           float* adam_m_dev, float* adam_v_dev, int64_t n_params, float lr, float beta1, float beta2,
+                           float eps, int step, int prev_fused, float grad_clip, const rlks_gather_next* next,
+                           void* workspace, int64_t ws_bytes, void* stream);
+/* rlks_ppo_adam_apply with clipping, after the caller's all-reduce(s) of rlks_ppo_grad_step[_next /
+ * _part]: the norm of the all-reduced gradient (every rank computes the same bits), then Adam on
+ * g * coef with the next step's weight maxima and step tag as rlks_ppo_adam_apply leaves them.
+ * stats_dev (may be NULL): the step's stats row, [RLKS_STAT_GRAD_GNORM] is written. */
+int rlks_ppo_adam_apply_clip(const rlks_mlp_desc* desc, float* params_dev, float* grad_dev, float* adam_m_dev,
+                             float* adam_v_dev, int64_t n_params, float lr, float beta1, float beta2, float eps,
+                             int step, float grad_clip, double* stats_dev, void* workspace, int64_t ws_bytes, int rows,
+                             void* stream);
 
 /* RLlib update_kl: kl = stats_sum[0] / stats_sum[1]; x1.5 if kl > 2*target, x0.5 if < target/2 */
 int rlks_kl_update(float* dyn_dev, const double* kl_sum_count_dev, float kl_target, void* stream);

@@ -131,6 +131,8 @@ enum {
   RLKS_STAT_KL = 2,          /* sum of KL(old || new) */
   RLKS_STAT_ENTROPY = 3,     /* sum of entropy */
   RLKS_STAT_ROWS = 4,        /* rows */
+  RLKS_STAT_GRAD_GNORM = 5,  /* global norm of the gradient before clipping (the *_clip entry points of
+                                rlks.h; every other entry point writes 0.0) */
   RLKS_STAT_SIZE = 8
 };
 

@@ -66,7 +66,54 @@ struct RedArgs {
   unsigned tag_val;
 };
 
-__device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
+// ----------------------------------------------------------------------------- global-norm clipping
+// RLlib's torch policy clips by global norm (ray/rllib/utils/torch_utils.py apply_grad_clipping ->
+// torch.nn.utils.clip_grad_norm_ over every parameter of the one optimizer): norm = sqrt(sum g^2),
+// coef = min(1, grad_clip / (norm + 1e-6)), g <- g coef, then Adam on the clipped g.  RLlib and torch
+// are third-party and absent here: the semantics are restated in tests/clip_ref.py.
+//
+// The sum of squares is an f64 sum in one fixed order that does not depend on how a kernel tiles the
+// gradient: per tensor, the zero-padded binary tree over the output-vector index (neighbours first:
+// x[i] + x[i ^ 1], then pairs of pairs, ...), then the tensors in task order.  A reduce block owns an
+// aligned power-of-two run of vectors, so its partial is one node of that tree whatever its size
+// (adding the +0.0 of a missing leaf is exact), and k_norm_finish continues the tree over the blocks.
+// The gradient reduce of the fused step (many partials, small blocks) and the one-partial pass over an
+// all-reduced gradient (1,024-element blocks) therefore give the same bits.  No atomics, no grid sync.
+struct NrmArgs {
+  double* part;       // RED_NRM / RED_NRM_ONLY: [reduce blocks] the block's sum of squares of its outputs
+  const float* coef;  // RED_CLIP: the clip coefficient k_norm_finish left
+};
+enum RedMode {
+  RED_PLAIN = 0,     // the reduce as it always was
+  RED_NRM = 1,       // + one norm partial per block
+  RED_NRM_ONLY = 2,  // one partial in place: norm partials only, nothing is written back
+  RED_CLIP = 3       // one partial in place: g <- g coef, written back, then the fused Adam
+};
+
+// g coef as one rounded fp32 product (IEEE round to nearest).  The pragma keeps it one: with hipcc's
+// default contraction the compiler would fold it into the Adam arithmetic that consumes it
+// (g coef - m as one fma), and the clipped step would differ from Adam on the stored clipped gradient.
+__device__ __forceinline__ float clip_mul(float g, float coef) {
+#pragma clang fp contract(off)
+  return g * coef;
+}
+
+__device__ __forceinline__ double tree64(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+// the 256 threads' values summed as the binary tree over threadIdx.x (every thread gets the sum)
+__device__ __forceinline__ double block_tree256(double v) {
+  __shared__ double w[4];
+  v = tree64(v);
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+template <int MODE>
+__device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx, const NrmArgs& c) {
   __shared__ double sh[4][256];
   int ti = 0;
   while (ti + 1 < g.ntasks && bx >= g.t[ti + 1].blk0) ++ti;
@@ -81,7 +128,9 @@ __device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
   constexpr int RB = 8;
   if (T.V == 4) {
     if (4 * iv < T.len) {
-      const float* base = T.part + 4 * iv;
+      // (kq 2, norm-only pass: the vector read where kq 1 writes it, so that a [256][256] weight's
+      // vectors are numbered as in the gradient reduce and the norm's tree is the same)
+      const float* base = T.part + ((MODE == RED_NRM_ONLY && T.kq == 2) ? (iv & 255) * 256 + 4 * (iv >> 8) : 4 * iv);
       int p = grp;
       for (; p + (RB - 1) * T.G < T.P; p += RB * T.G) {
         float4 v[RB];
@@ -121,6 +170,7 @@ __device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
   }
   __syncthreads();
   float wmax = 0.f;
+  double sq = 0.0;  // RED_NRM*: this thread's leaf of the norm's tree (its vector's sum of squares)
   if (grp == 0) {
     double t[4] = {0.0, 0.0, 0.0, 0.0};
     for (int j = 0; j < T.V; ++j) t[j] = sh[j][o];
@@ -128,8 +178,15 @@ __device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
     if (T.out64) {
       for (int j = 0; j < T.V && i0 + j < T.len; ++j) T.out64[i0 + j] = t[j];
     } else if (T.V == 4 && i0 + 3 < T.len) {
-      const float4 gv = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-      *reinterpret_cast<float4*>(T.out + i0) = gv;
+      float4 gv = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
+      if (MODE == RED_NRM || MODE == RED_NRM_ONLY)
+        sq = ((double)gv.x * (double)gv.x + (double)gv.y * (double)gv.y) +
+             ((double)gv.z * (double)gv.z + (double)gv.w * (double)gv.w);
+      if (MODE == RED_CLIP) {
+        const float cf = *c.coef;
+        gv = make_float4(clip_mul(gv.x, cf), clip_mul(gv.y, cf), clip_mul(gv.z, cf), clip_mul(gv.w, cf));
+      }
+      if (MODE != RED_NRM_ONLY) *reinterpret_cast<float4*>(T.out + i0) = gv;
       if (g.p) {  // Adam on the four parameters (16-byte aligned: tensors start on 64-float boundaries)
         const int64_t pi = (T.out - g.grad) + i0;
         float4 pv = *reinterpret_cast<const float4*>(g.p + pi), mv = *reinterpret_cast<const float4*>(g.m + pi),
@@ -145,10 +202,15 @@ __device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
         *reinterpret_cast<float4*>(g.v + pi) = vv;
       }
     } else {
+      double e2[4] = {0.0, 0.0, 0.0, 0.0};
       for (int j = 0; j < T.V && i0 + j < T.len; ++j) {
-        T.out[i0 + j] = (float)t[j];
-        if (g.p) wmax = fmaxf(wmax, fabsf(adam_elem(g.p, g.m, g.v, (T.out - g.grad) + i0 + j, (float)t[j], g.co)));
+        float gj = (float)t[j];
+        if (MODE == RED_NRM || MODE == RED_NRM_ONLY) e2[j] = (double)gj * (double)gj;
+        if (MODE == RED_CLIP) gj = clip_mul(gj, *c.coef);
+        if (MODE != RED_NRM_ONLY) T.out[i0 + j] = gj;
+        if (g.p) wmax = fmaxf(wmax, fabsf(adam_elem(g.p, g.m, g.v, (T.out - g.grad) + i0 + j, gj, g.co)));
       }
+      if (MODE == RED_NRM || MODE == RED_NRM_ONLY) sq = (e2[0] + e2[1]) + (e2[2] + e2[3]);
     }
   }
   if (g.p && T.mslot >= 0) {  // block-uniform: this block's max |w_new| -> the slot
@@ -168,14 +230,87 @@ __device__ __forceinline__ void reduce_block(const RedArgs& g, const int bx) {
     *g.tag[0] = g.tag_val;
     *g.tag[1] = g.tag_val;
   }
+  if (MODE == RED_NRM || MODE == RED_NRM_ONLY) {  // grp 0 is threads [0, opb): the rest add +0.0
+    const double bs = block_tree256(sq);
+    if (threadIdx.x == 0) c.part[bx] = bs;
+  }
 }
 
-__global__ __launch_bounds__(256) void k_reduce(RedArgs g) { reduce_block(g, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void k_reduce(RedArgs g) { reduce_block<RED_PLAIN>(g, (int)blockIdx.x, NrmArgs{}); }
+template <int MODE>
+__global__ __launch_bounds__(256) void k_reduce_clip(RedArgs g, NrmArgs c) {
+  reduce_block<MODE>(g, (int)blockIdx.x, c);
+}
+
+// The norm's tree continued over the reduce blocks' partials, one 256-thread block: per tensor k the
+// nb[k] partials from blk0[k] on, 64 at a time per wave (level 0: from memory, all tensors' chunks
+// numbered through by c0[k]; level 1: over level 0's sums), then up to 16 level-1 sums per tensor by
+// one thread, then the tensors in order.  norm = sqrt(S), coef = (float)min(1, clip / (norm + 1e-6)).
+constexpr int NRM_MAX_CHUNKS = 4096;  // level-0 sums held in LDS (64 partials each)
+constexpr int NRM_MAX_NB = 65536;     // partials per tensor (64 x 64 x 16)
+struct NrmPlan {
+  int n;
+  int blk0[RLKS_N_TENSORS], nb[RLKS_N_TENSORS], c0[RLKS_N_TENSORS + 1];
+};
+__global__ __launch_bounds__(256) void k_norm_finish(NrmPlan pl, const double* __restrict__ part, float clip,
+                                                     double* __restrict__ norm_ws, float* __restrict__ coef_ws,
+                                                     double* __restrict__ norm_out, double* __restrict__ stats) {
+  __shared__ double l0[NRM_MAX_CHUNKS];
+  __shared__ double l1[RLKS_N_TENSORS][16];
+  __shared__ double ts[RLKS_N_TENSORS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int ch = wave; ch < pl.c0[pl.n]; ch += 4) {
+    int k = 0;
+    while (k + 1 < pl.n && ch >= pl.c0[k + 1]) ++k;
+    const int i = (ch - pl.c0[k]) * 64 + lane;
+    const double v = tree64(i < pl.nb[k] ? part[pl.blk0[k] + i] : 0.0);
+    if (lane == 0) l0[ch] = v;
+  }
+  __syncthreads();
+  for (int k = wave; k < pl.n; k += 4) {
+    const int n1 = pl.c0[k + 1] - pl.c0[k];
+    for (int c2 = 0; c2 < 16; ++c2) {
+      const int i = c2 * 64 + lane;
+      const double v = c2 * 64 < n1 ? tree64(i < n1 ? l0[pl.c0[k] + i] : 0.0) : 0.0;  // (wave-uniform)
+      if (lane == 0) l1[k][c2] = v;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < pl.n) {
+    const double* e = l1[threadIdx.x];
+    ts[threadIdx.x] = (((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7]))) +
+                      (((e[8] + e[9]) + (e[10] + e[11])) + ((e[12] + e[13]) + (e[14] + e[15])));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double S = 0.0;
+    for (int k = 0; k < pl.n; ++k) S += ts[k];
+    const double norm = sqrt(S);
+    if (norm_ws) *norm_ws = norm;
+    if (coef_ws) *coef_ws = (float)fmin(1.0, (double)clip / (norm + 1e-6));
+    if (norm_out) *norm_out = norm;
+    if (stats) stats[RLKS_STAT_GRAD_GNORM] = norm;
+  }
+}
 
 struct Reducer {
   RedArgs a{};
   int blocks = 0;
   int mnext[4] = {0, 0, 0, 0};  // next free entry per max slot
+  int nblk[MAX_TASKS] = {};
+  // the parameter-gradient tasks' blocks, for k_norm_finish (the stats tasks are not part of the norm)
+  bool plan(NrmPlan& pl) const {
+    pl = NrmPlan{};
+    for (int i = 0; i < a.ntasks; ++i) {
+      if (a.t[i].out64) continue;
+      if (pl.n == RLKS_N_TENSORS || nblk[i] > NRM_MAX_NB) return false;
+      pl.blk0[pl.n] = a.t[i].blk0;
+      pl.nb[pl.n] = nblk[i];
+      pl.c0[pl.n + 1] = pl.c0[pl.n] + (int)cdiv(nblk[i], 64);
+      ++pl.n;
+    }
+    return pl.c0[pl.n] <= NRM_MAX_CHUNKS;
+  }
   void add(const float* part, float* out, double* out64, int64_t pstride, int P, int len, int mslot = -1) {
     RedTask& t = a.t[a.ntasks++];
     t.mslot = mslot;
@@ -189,6 +324,7 @@ struct Reducer {
     t.V = vec ? 4 : 1;
     t.blk0 = blocks;
     const int nb = (int)cdiv(cdiv(len, t.V), 256 / G);
+    nblk[a.ntasks - 1] = nb;
     blocks += nb;
     if (mslot >= 0) {
       t.mbase = mnext[mslot];
@@ -234,6 +370,16 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   (void)adam_elem(p, m, v, i, g[i], co);
+}
+
+// the same on the clipped gradient g coef (k_norm_finish's coefficient), which replaces g
+__global__ void k_adam_clip(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, int64_t n, AdamCo co, const float* __restrict__ coef) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float gi = clip_mul(g[i], *coef);
+  g[i] = gi;
+  (void)adam_elem(p, m, v, i, gi, co);
 }
 
 // RLlib PPO update_kl
@@ -423,7 +569,17 @@ struct NextGather {
 template <int S, int PS>
 __global__ __launch_bounds__(256) void k_reduce_gather(RedArgs g, NextGather n) {
   if ((int)blockIdx.x < n.blk0) {
-    reduce_block(g, (int)blockIdx.x);
+    reduce_block<RED_PLAIN>(g, (int)blockIdx.x, NrmArgs{});
+    return;
+  }
+  gather_packed_elem<S, PS>(n.perm, n.row0g, n.rows_g, n.Ng, n.N, n.rows, n.packed, n.mb,
+                            ((uint32_t)blockIdx.x - (uint32_t)n.blk0) * 256u + threadIdx.x);
+}
+// the same with the norm partials of the clipped step (rlks_ppo_sgd_step_clip)
+template <int S, int PS>
+__global__ __launch_bounds__(256) void k_reduce_gather_nrm(RedArgs g, NextGather n, NrmArgs c) {
+  if ((int)blockIdx.x < n.blk0) {
+    reduce_block<RED_NRM>(g, (int)blockIdx.x, c);
     return;
   }
   gather_packed_elem<S, PS>(n.perm, n.row0g, n.rows_g, n.Ng, n.N, n.rows, n.packed, n.mb,
@@ -803,7 +959,85 @@ int rlks_policy_forward_ws(const rlks_mlp_desc* d, const float* params, const fl
   return wide_forward(d, params, obs, d->obs_dim, n, w, logits, values, (hipStream_t)stream);
 }
 
-int rlks_ppo_workspace_bytes(const rlks_mlp_desc* d, int rows, int64_t* bytes) {
+}  // extern "C"
+
+namespace rlks {
+
+// One parameter-gradient task per tensor over the flat gradient g as a single partial, summed in
+// place (each element read and written by one thread): the reducer of the Adam pass after an
+// all-reduce, of the clipped Adam pass and of the norm pass.  slots: the W2 / W1a tasks feed the next
+// operand split's max |w| slots (fused Adam).  norm_order: a [256][256] W2 takes the vector numbering
+// of the gradient reduce (kq 2; reduce_block<RED_NRM_ONLY> only).
+static void flat_tasks(Reducer& R, const rlks_mlp_desc* d, const Layout& L, float* g, bool slots, bool norm_order) {
+  const int D = d->obs_dim, A = d->n_actions, H = d->hidden;
+  for (int net = 0; net < 2; ++net) {
+    const int An = net == 0 ? A : 1;
+    const int64_t* o = L.off + 6 * net;
+    R.add(g + o[0], g + o[0], nullptr, 0, 1, H * D, slots ? 2 * net + 1 : -1);
+    R.add(g + o[1], g + o[1], nullptr, 0, 1, H, slots ? 2 * net + 1 : -1);
+    R.add(g + o[2], g + o[2], nullptr, 0, 1, H * H, slots ? 2 * net : -1);
+    if (norm_order) R.a.t[R.a.ntasks - 1].kq = 2;
+    R.add(g + o[3], g + o[3], nullptr, 0, 1, H);
+    R.add(g + o[4], g + o[4], nullptr, 0, 1, An * H);
+    R.add(g + o[5], g + o[5], nullptr, 0, 1, An);
+  }
+}
+// the fused 256-unit kernels' gradient reduce numbers W2's vectors in k_sf_dw2r's partial order
+static bool norm_order(const rlks_mlp_desc* d) { return is_sf(d) && !is_wide(d); }
+
+// The clip's scratch, behind the gradient workspace of `rows` rows (rlks_ppo_workspace_bytes counts
+// it): the reduce blocks' norm partials, then the norm (f64) and the coefficient (f32).
+struct NrmWs {
+  double* part;
+  double* norm;
+  float* coef;
+  int cap;  // partials
+  int64_t bytes;
+};
+static NrmWs nrm_ws(const rlks_mlp_desc* d, char* base) {
+  const Layout L = make_layout(d->obs_dim, d->hidden, d->n_actions);
+  NrmWs w{};
+  if (norm_order(d)) {
+    // the fused step's gradient reduce: at most one block per output vector
+    w.cap = (int)(L.padded / 4) + 64;
+  } else {
+    Reducer R;
+    flat_tasks(R, d, L, nullptr, false, false);
+    w.cap = R.blocks;
+  }
+  const int64_t pb = (8LL * w.cap + 255) / 256 * 256;
+  w.part = (double*)base;
+  w.norm = (double*)(base ? base + pb : nullptr);
+  w.coef = (float*)(base ? base + pb + 8 : nullptr);
+  w.bytes = pb + 256;
+  return w;
+}
+
+// sum g^2 of the block partials the plan names -> norm, coefficient (and norm_out / stats[GRAD_GNORM])
+static int norm_finish(const Reducer& R, const NrmWs& n, float clip, double* norm_out, double* stats, hipStream_t s) {
+  NrmPlan pl;
+  RLKS_REQUIRE(R.blocks <= n.cap && R.plan(pl), RLKS_ERR_UNSUPPORTED, "grad_clip: too many reduce blocks for the norm");
+  hipLaunchKernelGGL(k_norm_finish, dim3(1), dim3(256), 0, s, pl, n.part, clip, n.norm, n.coef, norm_out, stats);
+  RLKS_LAUNCHED();
+  return RLKS_OK;
+}
+
+// the norm of the flat gradient g (one partial, nothing written back) -> n.norm / n.coef, norm_out, stats
+static int norm_pass(const rlks_mlp_desc* d, const float* g, const NrmWs& n, float clip, double* norm_out,
+                     double* stats, hipStream_t s) {
+  const Layout L = make_layout(d->obs_dim, d->hidden, d->n_actions);
+  Reducer R;
+  flat_tasks(R, d, L, const_cast<float*>(g), false, norm_order(d));
+  RLKS_REQUIRE(R.blocks <= n.cap, RLKS_ERR_UNSUPPORTED, "grad_clip: too many reduce blocks for the norm");
+  hipLaunchKernelGGL(k_reduce_clip<RED_NRM_ONLY>, dim3(R.blocks), dim3(256), 0, s, R.a, NrmArgs{n.part, nullptr});
+  RLKS_LAUNCHED();
+  return norm_finish(R, n, clip, norm_out, stats, s);
+}
+
+static bool clip_ok(float c) { return std::isfinite(c) && c > 0.f; }
+
+// the gradient workspace of `rows` rows alone, without the clip's scratch behind it
+static int grad_ws_bytes(const rlks_mlp_desc* d, int rows, int64_t* bytes) {
   if (int rc = check_desc(d)) return rc;
   if (is_wide(d)) {
     RLKS_REQUIRE(bytes && rows > 0, RLKS_ERR_ARG, "rlks_ppo_workspace_bytes: bad argument");
@@ -820,6 +1054,37 @@ int rlks_ppo_workspace_bytes(const rlks_mlp_desc* d, int rows, int64_t* bytes) {
                "rlks_ppo_workspace_bytes: rows must be a positive multiple of 128");
   *bytes = ws_layout(d->obs_dim, d->n_actions, rows, nullptr).bytes;
   return RLKS_OK;
+}
+
+// the clip's scratch inside the caller's workspace of `rows` gradient rows
+static int nrm_ws_at(const rlks_mlp_desc* d, int rows, void* workspace, int64_t ws_bytes, NrmWs& n) {
+  int64_t gb = 0;
+  if (int rc = grad_ws_bytes(d, rows, &gb)) return rc;
+  gb = (gb + 255) / 256 * 256;
+  n = nrm_ws(d, (char*)workspace + gb);
+  RLKS_REQUIRE(ws_bytes >= gb + n.bytes, RLKS_ERR_ARG, "grad_clip: workspace too small (rlks_ppo_workspace_bytes)");
+  return RLKS_OK;
+}
+
+}  // namespace rlks
+
+extern "C" {
+
+int rlks_ppo_workspace_bytes(const rlks_mlp_desc* d, int rows, int64_t* bytes) {
+  if (int rc = grad_ws_bytes(d, rows, bytes)) return rc;
+  *bytes = (*bytes + 255) / 256 * 256 + nrm_ws(d, nullptr).bytes;
+  return RLKS_OK;
+}
+
+int rlks_grad_global_norm(const rlks_mlp_desc* d, const float* grad, int64_t n_params, double* norm_dev,
+                          void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  RLKS_REQUIRE(grad && norm_dev && workspace, RLKS_ERR_ARG, "rlks_grad_global_norm: null argument");
+  RLKS_REQUIRE(n_params == make_layout(d->obs_dim, d->hidden, d->n_actions).padded, RLKS_ERR_ARG,
+               "rlks_grad_global_norm: n_params must be the padded layout size");
+  const NrmWs n = nrm_ws(d, (char*)workspace);
+  RLKS_REQUIRE(ws_bytes >= n.bytes, RLKS_ERR_ARG, "rlks_grad_global_norm: workspace too small");
+  return norm_pass(d, grad, n, 1.f, norm_dev, nullptr, (hipStream_t)stream);
 }
 
 int rlks_debug_sf_handoff(const rlks_mlp_desc* d, int rows, void* ws, void** out) {
@@ -856,6 +1121,7 @@ struct FusedAdam {
   bool apply = true;  // false: the prep uses the previous step's maxima, the reduce only sums (an
                       // all-reduce follows; rlks_ppo_adam_apply then applies Adam)
   int64_t n = 0;      // parameter count, for the unfused Adam pass of the fp32 / wide paths (sgd_step)
+  float clip = 0.f;   // > 0 (with apply): global-norm clipping, Adam as a pass of its own after the norm
 };
 
 // part: 0 = the whole gradient; 1 = the weight split, F1a, F2 and the reduce of W2 / b2 / W3 / b3 and
@@ -863,7 +1129,8 @@ struct FusedAdam {
 // 1's buckets while part 2 runs)
 static int sf_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* params, const float* dyn,
                    const float* mb, int M, float* grad, double* stats, void* workspace, int64_t ws_bytes, int phases,
-                   hipStream_t s, const FusedAdam* fa = nullptr, const NextGather* nx = nullptr, int part = 0) {
+                   hipStream_t s, const FusedAdam* fa = nullptr, const NextGather* nx = nullptr, int part = 0,
+                   const NrmWs* nrm = nullptr, float clip = 0.f) {
   RLKS_REQUIRE(M > 0 && M % 256 == 0, RLKS_ERR_ARG, "rlks_ppo_grad: split-fp16 rows must be a positive multiple of 256");
   const int D = d->obs_dim, A = d->n_actions, H = HID;
   const SfWs w = sf_ws_layout(D, A, M, (char*)workspace);
@@ -937,6 +1204,24 @@ static int sf_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const floa
     RLKS_REQUIRE(part == 0, RLKS_ERR_ARG, "sf_grad: fused Adam needs the whole gradient");
     RLKS_REQUIRE(R.adam(fa->p, fa->m, fa->v, grad, fa->co, fa->step, w.w), RLKS_ERR_UNSUPPORTED,
                  "rlks_ppo_sgd_step: too many reduce blocks per weight");
+  }
+  if (nrm) {  // the clipped step: the same reduce (and gather) with one norm partial per block, then the norm
+    RLKS_REQUIRE(part == 0 && !(fa && fa->apply), RLKS_ERR_ARG, "sf_grad: the norm needs the whole, unapplied gradient");
+    RLKS_REQUIRE(R.blocks <= nrm->cap, RLKS_ERR_UNSUPPORTED, "grad_clip: too many reduce blocks for the norm");
+    const NrmArgs c{nrm->part, nullptr};
+    if (nx && nx->rows > 0) {
+      NextGather n = *nx;
+      n.blk0 = R.blocks;
+      const int ps = rlks_packed_stride(d), stride = mb_stride(D, A);
+      const dim3 grid(R.blocks + (int)cdiv((int64_t)n.rows * ps / 4, 256));
+      if (stride == 12) hipLaunchKernelGGL((k_reduce_gather_nrm<12, 16>), grid, dim3(256), 0, s, R.a, n, c);
+      else if (stride == 20) hipLaunchKernelGGL((k_reduce_gather_nrm<20, 32>), grid, dim3(256), 0, s, R.a, n, c);
+      else hipLaunchKernelGGL((k_reduce_gather_nrm<36, 48>), grid, dim3(256), 0, s, R.a, n, c);
+    } else {
+      hipLaunchKernelGGL(k_reduce_clip<RED_NRM>, dim3(R.blocks), dim3(256), 0, s, R.a, c);
+    }
+    RLKS_LAUNCHED();
+    return norm_finish(R, *nrm, clip, nullptr, stats, s);
   }
   if (nx && nx->rows > 0) {  // + the next step's gather (blocks after the reduce's)
     NextGather n = *nx;
@@ -1101,6 +1386,39 @@ static int adam_pass(float* p, const float* g, float* m, float* v, int64_t n, co
   return RLKS_OK;
 }
 
+static int adam_clip_pass(float* p, float* g, float* m, float* v, int64_t n, const AdamCo& co, const float* coef,
+                          void* stream) {
+  RLKS_REQUIRE(p && g && m && v && n >= 0, RLKS_ERR_ARG, "rlks_ppo_adam_apply_clip: bad argument");
+  if (n == 0) return RLKS_OK;
+  hipLaunchKernelGGL(k_adam_clip, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, co, coef);
+  RLKS_LAUNCHED();
+  return RLKS_OK;
+}
+
+// Adam over the flat gradient as a reduce over one partial that also leaves the new weights' maxima
+// and the step tag (rlks_ppo_adam_apply); coef: first g <- g coef, written back (the clipped pass)
+static int sf_adam_apply(const rlks_mlp_desc* d, float* params, float* grad, float* adam_m, float* adam_v,
+                         const AdamCo& co, int step, void* workspace, int64_t ws_bytes, int rows, const float* coef,
+                         hipStream_t s) {
+  RLKS_REQUIRE(rows > 0 && rows % 256 == 0, RLKS_ERR_ARG, "rlks_ppo_adam_apply: rows as in rlks_ppo_grad_step");
+  const SfWs w = sf_ws_layout(d->obs_dim, d->n_actions, rows, (char*)workspace);
+  RLKS_REQUIRE(ws_bytes >= w.bytes, RLKS_ERR_ARG, "rlks_ppo_adam_apply: workspace too small");
+  const Layout L = make_layout(d->obs_dim, HID, d->n_actions);
+  Reducer R;
+  flat_tasks(R, d, L, grad, true, false);
+  RLKS_REQUIRE(R.adam(params, adam_m, adam_v, grad, co, step, w.w), RLKS_ERR_UNSUPPORTED,
+               "rlks_ppo_adam_apply: too many blocks per weight");
+  if (coef) hipLaunchKernelGGL(k_reduce_clip<RED_CLIP>, dim3(R.blocks), dim3(256), 0, s, R.a, NrmArgs{nullptr, coef});
+  else hipLaunchKernelGGL(k_reduce, dim3(R.blocks), dim3(256), 0, s, R.a);
+  RLKS_LAUNCHED();
+  return RLKS_OK;
+}
+
+// gradient only: the prep reads the previous step's maxima when prev_fused, the reduce only sums
+static FusedAdam grad_only(int step, int prev_fused) {
+  return FusedAdam{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
+}
+
 int rlks_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, int step, void* stream) {
   RLKS_REQUIRE(step >= 1, RLKS_ERR_ARG, "rlks_adam_step: bad argument");
@@ -1158,12 +1476,22 @@ static int sgd_step_any(const StepArgs& a, const char* bad_arg, const FusedAdam&
   RLKS_REQUIRE(a.co && a.params && a.dyn && a.mb && a.grad && a.workspace && fa.step >= 1 &&
                    (!fa.apply || (fa.m && fa.v)), RLKS_ERR_ARG, bad_arg);
   if (part == 1) x = nullptr;
+  const bool clip = fa.apply && fa.clip > 0.f;
+  NrmWs nw{};
+  if (clip) {
+    RLKS_REQUIRE(part == 0, RLKS_ERR_ARG, bad_arg);
+    if (int rc = nrm_ws_at(a.d, a.M, a.workspace, a.ws_bytes, nw)) return rc;
+  }
   if (!is_sf(a.d) || is_wide(a.d)) {
     if (part != 2) {
       if (int rc = rlks_ppo_grad(a.d, a.co, a.params, a.dyn, a.mb, a.M, a.grad, a.stats, a.workspace, a.ws_bytes, a.stream))
         return rc;
-      if (fa.apply)
+      if (clip) {  // the norm of the gradient, then Adam on g coef
+        if (int rc = norm_pass(a.d, a.grad, nw, fa.clip, nullptr, a.stats, (hipStream_t)a.stream)) return rc;
+        if (int rc = adam_clip_pass(fa.p, a.grad, fa.m, fa.v, fa.n, fa.co, nw.coef, a.stream)) return rc;
+      } else if (fa.apply) {
         if (int rc = adam_pass(fa.p, a.grad, fa.m, fa.v, fa.n, fa.co, a.stream)) return rc;
+      }
     }
     return x ? gather_after(a.d, x, a.stream) : RLKS_OK;
   }
@@ -1171,15 +1499,37 @@ static int sgd_step_any(const StepArgs& a, const char* bad_arg, const FusedAdam&
   bool fused = false;
   if (x)
     if (int rc = next_gather(a.d, x, n, fused)) return rc;
+  if (clip) {
+    // the gradient as the multi-rank step computes it (the reduce only sums; the next gather stays in
+    // its launch) with the norm partials, the norm, then the clipped Adam pass as a launch of its own
+    const FusedAdam g = grad_only(fa.step, fa.prev_fused);
+    if (int rc = sf_grad(a.d, a.co, a.params, a.dyn, a.mb, a.M, a.grad, a.stats, a.workspace, a.ws_bytes,
+                         RLKS_PHASE_ALL, (hipStream_t)a.stream, &g, fused ? &n : nullptr, 0, &nw, fa.clip))
+      return rc;
+    if (int rc = sf_adam_apply(a.d, fa.p, a.grad, fa.m, fa.v, fa.co, fa.step, a.workspace, a.ws_bytes, a.M, nw.coef,
+                               (hipStream_t)a.stream))
+      return rc;
+    return (x && !fused) ? gather_after(a.d, x, a.stream) : RLKS_OK;
+  }
   if (int rc = sf_grad(a.d, a.co, a.params, a.dyn, a.mb, a.M, a.grad, a.stats, a.workspace, a.ws_bytes, RLKS_PHASE_ALL,
                        (hipStream_t)a.stream, &fa, fused ? &n : nullptr, part))
     return rc;
   return (x && !fused) ? gather_after(a.d, x, a.stream) : RLKS_OK;
 }
 
-// gradient only: the prep reads the previous step's maxima when prev_fused, the reduce only sums
-static FusedAdam grad_only(int step, int prev_fused) {
-  return FusedAdam{nullptr, nullptr, nullptr, AdamCo{}, step, prev_fused ? 1 : 0, false};
+int rlks_ppo_sgd_step_clip(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, float* params, const float* dyn,
+                           const float* mb, int M, float* grad, double* stats, float* adam_m, float* adam_v,
+                           int64_t n_params, float lr, float beta1, float beta2, float eps, int step, int prev_fused,
+                           float grad_clip, const rlks_gather_next* x, void* workspace, int64_t ws_bytes,
+                           void* stream) {
+  RLKS_REQUIRE(clip_ok(grad_clip), RLKS_ERR_ARG, "rlks_ppo_sgd_step_clip: grad_clip must be finite and > 0");
+  if (int rc = check_desc(d)) return rc;
+  RLKS_REQUIRE(n_params == make_layout(d->obs_dim, d->hidden, d->n_actions).padded, RLKS_ERR_ARG,
+               "rlks_ppo_sgd_step_clip: n_params must be the padded layout size");
+  const FusedAdam fa{params, adam_m, adam_v, adam_co(lr, beta1, beta2, eps, step), step, prev_fused ? 1 : 0, true,
+                     n_params, grad_clip};
+  return sgd_step_any({d, co, params, dyn, mb, M, grad, stats, workspace, ws_bytes, stream},
+                      "rlks_ppo_sgd_step_clip: bad argument", fa, x, 0);
 }
 
 int rlks_ppo_sgd_step_next(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, float* params, const float* dyn,
@@ -1235,29 +1585,31 @@ int rlks_ppo_adam_apply(const rlks_mlp_desc* d, float* params, const float* grad
                "rlks_ppo_adam_apply: bad argument");
   if (!is_sf(d) || is_wide(d))
     return rlks_adam_step(params, grad, adam_m, adam_v, n_params, lr, beta1, beta2, eps, step, stream);
-  RLKS_REQUIRE(rows > 0 && rows % 256 == 0, RLKS_ERR_ARG, "rlks_ppo_adam_apply: rows as in rlks_ppo_grad_step");
-  const int D = d->obs_dim, A = d->n_actions, H = HID;
-  const SfWs w = sf_ws_layout(D, A, rows, (char*)workspace);
-  RLKS_REQUIRE(ws_bytes >= w.bytes, RLKS_ERR_ARG, "rlks_ppo_adam_apply: workspace too small");
-  const Layout L = make_layout(D, H, A);
-  RLKS_REQUIRE(n_params == L.padded, RLKS_ERR_ARG, "rlks_ppo_adam_apply: n_params must be the padded layout size");
-  float* g = const_cast<float*>(grad);  // one partial, summed in place (each element read and written by one thread)
-  Reducer R;
-  for (int net = 0; net < 2; ++net) {
-    const int An = net == 0 ? A : 1;
-    const int64_t* o = L.off + 6 * net;
-    R.add(g + o[0], g + o[0], nullptr, 0, 1, H * D, 2 * net + 1);
-    R.add(g + o[1], g + o[1], nullptr, 0, 1, H, 2 * net + 1);
-    R.add(g + o[2], g + o[2], nullptr, 0, 1, H * H, 2 * net);
-    R.add(g + o[3], g + o[3], nullptr, 0, 1, H);
-    R.add(g + o[4], g + o[4], nullptr, 0, 1, An * H);
-    R.add(g + o[5], g + o[5], nullptr, 0, 1, An);
-  }
-  RLKS_REQUIRE(R.adam(params, adam_m, adam_v, grad, adam_co(lr, beta1, beta2, eps, step), step, w.w),
-               RLKS_ERR_UNSUPPORTED, "rlks_ppo_adam_apply: too many blocks per weight");
-  hipLaunchKernelGGL(k_reduce, dim3(R.blocks), dim3(256), 0, (hipStream_t)stream, R.a);
-  RLKS_LAUNCHED();
-  return RLKS_OK;
+  RLKS_REQUIRE(n_params == make_layout(d->obs_dim, HID, d->n_actions).padded, RLKS_ERR_ARG,
+               "rlks_ppo_adam_apply: n_params must be the padded layout size");
+  // one partial, summed in place (each element read and written by one thread)
+  return sf_adam_apply(d, params, const_cast<float*>(grad), adam_m, adam_v, adam_co(lr, beta1, beta2, eps, step), step,
+                       workspace, ws_bytes, rows, nullptr, (hipStream_t)stream);
+}
+
+int rlks_ppo_adam_apply_clip(const rlks_mlp_desc* d, float* params, float* grad, float* adam_m, float* adam_v,
+                             int64_t n_params, float lr, float beta1, float beta2, float eps, int step,
+                             float grad_clip, double* stats, void* workspace, int64_t ws_bytes, int rows,
+                             void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  RLKS_REQUIRE(params && grad && adam_m && adam_v && workspace && step >= 1, RLKS_ERR_ARG,
+               "rlks_ppo_adam_apply_clip: bad argument");
+  RLKS_REQUIRE(clip_ok(grad_clip), RLKS_ERR_ARG, "rlks_ppo_adam_apply_clip: grad_clip must be finite and > 0");
+  RLKS_REQUIRE(n_params == make_layout(d->obs_dim, d->hidden, d->n_actions).padded, RLKS_ERR_ARG,
+               "rlks_ppo_adam_apply_clip: n_params must be the padded layout size");
+  NrmWs nw;
+  if (int rc = nrm_ws_at(d, rows, workspace, ws_bytes, nw)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // the norm of the (all-reduced) gradient, then Adam on g coef
+  if (int rc = norm_pass(d, grad, nw, grad_clip, nullptr, stats, s)) return rc;
+  const AdamCo co = adam_co(lr, beta1, beta2, eps, step);
+  if (!is_sf(d) || is_wide(d)) return adam_clip_pass(params, grad, adam_m, adam_v, n_params, co, nw.coef, stream);
+  return sf_adam_apply(d, params, grad, adam_m, adam_v, co, step, workspace, ws_bytes, rows, nw.coef, s);
 }
 
 int rlks_kl_update(float* dyn, const double* kc, float target, void* stream) {

@@ -24,6 +24,7 @@ RLKS_PHASE_FWD, RLKS_PHASE_DW2, RLKS_PHASE_DH1, RLKS_PHASE_REDUCE, RLKS_PHASE_AL
 RLKS_PHASE_FWD_PI, RLKS_PHASE_FWD_VF, RLKS_PHASE_PREP, RLKS_PHASE_F1A, RLKS_PHASE_F1B = 16, 32, 64, 128, 256
 RLKS_PRECISION_FP32, RLKS_PRECISION_SF16, RLKS_PRECISION_WIDE, RLKS_PRECISION_F16 = 0, 1, 2, 3
 RLKS_STAT_POLICY_LOSS, RLKS_STAT_VF_LOSS, RLKS_STAT_KL, RLKS_STAT_ENTROPY, RLKS_STAT_ROWS = 0, 1, 2, 3, 4
+RLKS_STAT_GRAD_GNORM = 5
 RLKS_EPLOG_CAP = 128
 
 
@@ -141,6 +142,11 @@ SIGNATURES = {
     "rlks_ppo_grad_step_part": [C.POINTER(MlpDesc), C.POINTER(PpoCoeffs), _P, _P, _P, _I, _P, _P, _I, _I, _I,
                                 C.POINTER(GatherNext), _P, _I64, _P],
     "rlks_ppo_adam_apply": [C.POINTER(MlpDesc), _P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _P, _I64, _I, _P],
+    "rlks_grad_global_norm": [C.POINTER(MlpDesc), _P, _I64, _P, _P, _I64, _P],
+    "rlks_ppo_sgd_step_clip": [C.POINTER(MlpDesc), C.POINTER(PpoCoeffs), _P, _P, _P, _I, _P, _P, _P, _P, _I64, _F,
+                               _F, _F, _F, _I, _I, _F, C.POINTER(GatherNext), _P, _I64, _P],
+    "rlks_ppo_adam_apply_clip": [C.POINTER(MlpDesc), _P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _F, _P, _P, _I64, _I,
+                                 _P],
     "rlks_kl_update": [_P, _P, _F, _P],
 }
 _RESTYPES = {"rlks_last_error": C.c_char_p, "rlks_version": C.c_char_p}

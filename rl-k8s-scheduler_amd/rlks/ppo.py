@@ -19,7 +19,8 @@ One PPO iteration on one GPU (all launches on torch's current stream, no host sy
             rlks_adam_step); then rlks_kl_update from the mean KL over all SGD steps.  Single rank:
             rlks_ppo_sgd_step_next per minibatch (gradient + Adam, and the next minibatch's gather
             inside the same reduce launch); ranks: rlks_ppo_grad_step_next -> all-reduce ->
-            rlks_ppo_adam_apply
+            rlks_ppo_adam_apply.  With config.grad_clip (global-norm clipping, include/rlks.h):
+            rlks_ppo_sgd_step_clip, or rlks_ppo_adam_apply_clip after the all-reduce
 Multi-GPU (torch.distributed, backend "nccl" = RCCL): each rank owns a contiguous block of lanes
 (env_offset = rank * lanes), the flat gradient and the few scalar sums are all-reduced.
 """
@@ -39,6 +40,7 @@ from . import _lib
 from . import distributed as ddp
 from .env import DeviceEnv, make_cfg
 from .policy import PolicyParams
+from .schedules import schedule_value, validate_grad_clip, validate_schedule
 from .tables import load_table
 
 
@@ -64,7 +66,17 @@ class PPOConfig:
         self.entropy_coeff = 0.0
         self.kl_coeff = 0.2
         self.kl_target = 0.01
+        # RLlib's global-norm gradient clipping (apply_grad_clipping -> torch clip_grad_norm_ over both
+        # nets' parameters, one optimizer): None = off, else a finite positive norm bound; the norm
+        # before clipping is reported as learner_stats["grad_gnorm"].  grad_clip_by: only
+        # "global_norm" (RLlib's default) exists here, "value" / "norm" raise (rlks.schedules)
         self.grad_clip = None
+        self.grad_clip_by = None
+        # [[timestep, value], ...] from timestep 0, linear in between, the last value held
+        # (rlks.schedules): evaluated at timesteps_total when an iteration starts; when set they
+        # override lr / entropy_coeff
+        self.lr_schedule = None
+        self.entropy_coeff_schedule = None
         self.model = {"fcnet_hiddens": [256, 256], "fcnet_activation": "tanh", "vf_share_layers": False}
         self.num_gpus = 0
         self.seed = None
@@ -237,6 +249,10 @@ class PPO:
         self.config = cfg = (config or PPOConfig()).copy()
         if env is not None:
             cfg.env = env
+        self.grad_clip = validate_grad_clip(cfg.grad_clip, cfg.grad_clip_by)
+        for name in ("lr_schedule", "entropy_coeff_schedule"):
+            if getattr(cfg, name) is not None:
+                validate_schedule(getattr(cfg, name), name)
         self.torch = torch
         self.rank, self.world = ddp.rank_world()
         self.multi = self.world > 1 or ddp.forced()  # the multi-rank SGD step (ddp.forced: one rank, RCCL)
@@ -354,6 +370,7 @@ class PPO:
         self.sample_calls = 0   # compute_actions / compute_single_action draws so far (Philox counter)
         self.iteration = 0
         self.timesteps_total = 0
+        self._apply_schedules()
         from .metrics import JsonLinesReporter
 
         self.reporter = JsonLinesReporter.from_config(cfg, self.rank)
@@ -366,6 +383,16 @@ class PPO:
 
     def _allreduce(self, t):
         ddp.allreduce_sum_(t)
+
+    def _apply_schedules(self):
+        """the learning rate and entropy coefficient of the iteration that starts at timesteps_total
+        (checkpointed, so a resumed run continues its schedules exactly): the schedule's value where
+        one is set, else config.lr / config.entropy_coeff"""
+        cfg = self.config
+        ts = self.timesteps_total
+        self.cur_lr = float(cfg.lr) if cfg.lr_schedule is None else schedule_value(cfg.lr_schedule, ts)
+        self.coeffs.entropy_coeff = (float(cfg.entropy_coeff) if cfg.entropy_coeff_schedule is None
+                                     else schedule_value(cfg.entropy_coeff_schedule, ts))
 
     def rollout(self, explore=True):
         s = self.stream
@@ -416,10 +443,22 @@ class PPO:
             ne, nb = next_mb
             nxt = C.byref(_lib.GatherNext(_lib.ptr(self.packed), _lib.ptr(self.mbuf), self.perm_seed(), nb * self.mb,
                                           self.T, self.N, ne, self.groups, self.group0, self.mb))
+        lr = self.cur_lr if self.config.lr_schedule is not None else float(self.config.lr)
+        clip = self.grad_clip
+        if not self.multi and clip is not None:
+            # clipped: the gradient launches (norm partials from the reduce, the next gather inside
+            # it), the norm, then the clipped Adam pass (rlks_ppo_sgd_step_clip)
+            _lib.call("rlks_ppo_sgd_step_clip", desc, C.byref(self.coeffs), _lib.ptr(self.params.flat),
+                      _lib.ptr(self.dyn), _lib.ptr(self.mbuf), self.mb, _lib.ptr(self.grad), _lib.ptr(stat_row),
+                      _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self.params.padded, lr, float(beta1),
+                      float(beta2), float(self.config.adam_eps), self.adam_step, int(self._fused_prev), clip,
+                      nxt, _lib.ptr(self.ws), self.ws.numel(), s)
+            self._fused_prev = True
+            return
         if not self.multi:  # no all-reduce between gradient and Adam: one fused launch sequence
             _lib.call("rlks_ppo_sgd_step_next", desc, C.byref(self.coeffs), _lib.ptr(self.params.flat),
                       _lib.ptr(self.dyn), _lib.ptr(self.mbuf), self.mb, _lib.ptr(self.grad), _lib.ptr(stat_row),
-                      _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self.params.padded, float(self.config.lr),
+                      _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self.params.padded, lr,
                       float(beta1), float(beta2), float(self.config.adam_eps), self.adam_step, int(self._fused_prev),
                       nxt, _lib.ptr(self.ws), self.ws.numel(), s)
             self._fused_prev = True
@@ -458,9 +497,15 @@ class PPO:
             if ev:
                 e1 = event()
                 self._ar_events.append((e0, e0, e1))
-        _lib.call("rlks_ppo_adam_apply", desc, _lib.ptr(self.params.flat), _lib.ptr(self.grad), _lib.ptr(self.adam_m),
-                  _lib.ptr(self.adam_v), self.params.padded, float(self.config.lr), float(beta1), float(beta2),
-                  float(self.config.adam_eps), self.adam_step, _lib.ptr(self.ws), self.ws.numel(), self.mb, s)
+        if clip is not None:  # the norm of the all-reduced gradient (the same bits on every rank), then Adam
+            _lib.call("rlks_ppo_adam_apply_clip", desc, _lib.ptr(self.params.flat), _lib.ptr(self.grad),
+                      _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self.params.padded, lr, float(beta1), float(beta2),
+                      float(self.config.adam_eps), self.adam_step, clip, _lib.ptr(stat_row), _lib.ptr(self.ws),
+                      self.ws.numel(), self.mb, s)
+        else:
+            _lib.call("rlks_ppo_adam_apply", desc, _lib.ptr(self.params.flat), _lib.ptr(self.grad),
+                      _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self.params.padded, lr, float(beta1), float(beta2),
+                      float(self.config.adam_eps), self.adam_step, _lib.ptr(self.ws), self.ws.numel(), self.mb, s)
         self._fused_prev = True
 
     def update(self):
@@ -480,6 +525,7 @@ class PPO:
 
     def train_step_no_sync(self):
         """one PPO iteration, enqueued only (bench path)"""
+        self._apply_schedules()
         self.rollout(explore=self.config.explore)
         self.advantages()
         self.update()
@@ -596,8 +642,12 @@ class PPO:
             "kl": float(np.mean(st[:, _lib.RLKS_STAT_KL] / rows)),
             "entropy": float(np.mean(st[:, _lib.RLKS_STAT_ENTROPY] / rows)),
             "cur_kl_coeff": kl_before,
-            "cur_lr": float(self.config.lr),
+            "cur_lr": self.cur_lr,
         }
+        if self.grad_clip is not None:
+            # RLlib's grad_gnorm: the norm before clipping, a mean over the SGD steps.  Every rank
+            # wrote the same norm and self.stats was sum-all-reduced: divide by the world size
+            learner["grad_gnorm"] = float(np.mean(st[:, _lib.RLKS_STAT_GRAD_GNORM]) / self.world)
         result = {
             "episode_reward_mean": reward_mean,
             "episode_reward_mean_this_iter": float(ep[0] / n_ep) if n_ep else float("nan"),
@@ -781,6 +831,7 @@ class PPO:
         self.dyn[_lib.RLKS_DYN_KL_COEFF] = float(meta["kl_coeff"])
         self.iteration = int(meta["iteration"])
         self.timesteps_total = int(meta["timesteps_total"])
+        self._apply_schedules()
         self.episodes_total = int(meta["episodes_total"])
         self._ep_history.clear()
         self._ep_history.extend(meta.get("episode_history", []))
