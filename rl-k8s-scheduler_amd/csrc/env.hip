@@ -78,10 +78,23 @@ __global__ void k_mt_seed(EnvView v, const uint8_t* __restrict__ mask, const uin
   mt[MT_N * S + lane] = MT_N;
 }
 
+// obs row `row` from the lane's used millicores (exact ints, IEEE f32 divide)
+__device__ __forceinline__ void node_obs_row(const EnvView& v, const double* __restrict__ cost,
+                                             const double* __restrict__ lat, int lane, int row,
+                                             float* __restrict__ o) {
+  const int C = v.C;
+  for (int c = 0; c < C; ++c) o[c] = (float)cost[row * C + c];
+  for (int c = 0; c < C; ++c) o[C + c] = (float)lat[row * C + c];
+  for (int c = 0; c < C; ++c)
+    o[2 * C + c] = __fdiv_rn((float)v.used_cpu[(size_t)c * v.N + lane], (float)(v.nodes * v.cap[c]));
+}
+
+// (a node-level env reads row 0 of its tables from global memory, as its step kernels read theirs: its
+// tables are not staged and need not fit LDS, which 100 rows of more than 81 clusters do not)
 __global__ void k_env_reset(EnvView v, const double* __restrict__ cost, const double* __restrict__ lat,
                             const uint8_t* __restrict__ mask, float* __restrict__ obs) {
   extern __shared__ __attribute__((aligned(16))) double s_tab[];
-  stage_tables(s_tab, cost, lat, v.T * v.C);
+  if (v.nodes == 0) stage_tables(s_tab, cost, lat, v.T * v.C);
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= v.N) return;
   if (mask && !mask[lane]) return;
@@ -89,8 +102,13 @@ __global__ void k_env_reset(EnvView v, const double* __restrict__ cost, const do
   v.episode[lane] = ep;
   v.step[lane] = 0;
   v.ep_ret[lane] = 0.0;
-  if (v.nodes > 0) nodes_reset_lane(v, lane, ep);
-  emit_obs(v, s_tab, lane, 0, ep, obs + (size_t)lane * 3 * v.C);
+  float* o = obs + (size_t)lane * 3 * v.C;
+  if (v.nodes > 0) {
+    nodes_reset_lane(v, lane, ep);
+    node_obs_row(v, cost, lat, lane, 0, o);
+  } else {
+    emit_obs(v, s_tab, lane, 0, ep, o);
+  }
 }
 
 // node occupancy at creation (episode 0), so that stepping before the first reset is defined
@@ -325,17 +343,6 @@ __device__ __forceinline__ int flush_chunk(int2* col, uint16_t* tot, int ch, int
   return d;
 }
 
-// obs row `row` from the lane's used millicores (exact ints, IEEE f32 divide)
-__device__ __forceinline__ void node_obs_row(const EnvView& v, const double* __restrict__ cost,
-                                             const double* __restrict__ lat, int lane, int row,
-                                             float* __restrict__ o) {
-  const int C = v.C;
-  for (int c = 0; c < C; ++c) o[c] = (float)cost[row * C + c];
-  for (int c = 0; c < C; ++c) o[C + c] = (float)lat[row * C + c];
-  for (int c = 0; c < C; ++c)
-    o[2 * C + c] = __fdiv_rn((float)v.used_cpu[(size_t)c * v.N + lane], (float)(v.nodes * v.cap[c]));
-}
-
 // step counters of one lane (summed per wave into v.counters when enabled)
 struct NodeCounters {
   unsigned long long checks = 0, placed = 0, rej = 0, dep = 0, wr = 0, rd = 0;
@@ -343,7 +350,8 @@ struct NodeCounters {
 
 // u < S[x], the survival table's entry x (0 past the table), decided without reading the table
 // wherever the fp32 estimate (1 - p)^x 2^32 = exp2(x lg1p) 2^32 is more than 2^16 from u: the
-// estimate is within ~400 of S[x] for every x and p (tests/test_nodes_host.py checks the bound), so
+// estimate is within ~400 of S[x] for every x and p (tests/test_oracle_nodes.py::
+// test_departure_skip_estimate_bound checks the bound), so
 // only u within 2^16 of S[x] (~2^-15 of the draws) needs the table, and the answer is the table's.
 __device__ __forceinline__ bool u_below_S(const EnvView& v, const uint32_t* S, int x, uint32_t u, float lg1p) {
   const float e = exp2f((float)x * lg1p) * 0x1p32f;
@@ -997,7 +1005,9 @@ int rlks_env_create_ext(const rlks_env_cfg* cfg, const double* cost, const doubl
   RLKS_REQUIRE(cfg->max_steps > 0, RLKS_ERR_ARG, "rlks_env_create: max_steps must be positive");
   RLKS_REQUIRE(cfg->noise_mode == RLKS_NOISE_PHILOX || cfg->noise_mode == RLKS_NOISE_MT19937,
                RLKS_ERR_ARG, "rlks_env_create: unknown noise_mode");
-  RLKS_REQUIRE((size_t)2 * cfg->n_rows * cfg->n_clouds * sizeof(double) <= (size_t)MAX_TABLE_BYTES,
+  // (the reference env's kernels stage both tables in LDS; a node-level env's read them from global memory)
+  RLKS_REQUIRE(cfg->nodes_per_cluster > 0 ||
+                   (size_t)2 * cfg->n_rows * cfg->n_clouds * sizeof(double) <= (size_t)MAX_TABLE_BYTES,
                RLKS_ERR_UNSUPPORTED, "rlks_env_create: tables exceed the LDS budget");
   const int C = cfg->n_clouds, NN = cfg->nodes_per_cluster;
   if (NN > 0) {

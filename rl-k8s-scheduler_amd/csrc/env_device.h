@@ -291,6 +291,7 @@ __device__ __forceinline__ StepOut step_lane(const EnvView& v, const double* s_t
 }
 
 inline size_t table_lds(const rlks_env* e) {
+  if (e->cfg.nodes_per_cluster > 0) return 0;  // node-level envs do not stage their tables
   return (size_t)2 * e->cfg.n_rows * e->cfg.n_clouds * sizeof(double);
 }
 

@@ -163,3 +163,13 @@ def test_departures_are_geometric_per_pod(p):
     else:
         sd = np.sqrt(pods0 * p * (1 - p))
         assert abs(left - p * pods0) < 5 * sd
+
+
+@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E", "F", "G", "H", "I"])
+def test_regime_cases_are_in_their_regime(name):
+    """the cases tests/test_gpu_nodes_regimes.py holds the device to (tests/node_regimes.py) reject
+    pods, skip full chunks, fill whole clusters, outrun or exceed the survival table, ... in the
+    oracle: floors on the oracle's own counters and node state, about a tenth of what it gives"""
+    import node_regimes as nr
+
+    nr.check_guards(name)
