@@ -96,7 +96,17 @@ int rlks_env_step(rlks_env* env, const int32_t* actions_dev, float* obs_dev, dou
 /* Fused action sampling + step for the rollout (RLlib sampler + TorchCategorical): action =
  * Categorical(logits) via Philox (explore != 0) or argmax (explore == 0, compute_single_action
  * explore=False); logp of the chosen action; env step; auto-reset; episode-return tracking.
- * Table envs only (RLKS_ERR_UNSUPPORTED for node-level envs). */
+ * logits_dev is [n_envs][n_clouds] (row stride n_clouds); lane i's draw is Philox4x32-10 of the
+ * counter {env_offset + i, episode[i], step[i], RLKS_PURPOSE_ACTION << 16} under the env's seed,
+ * with the episode and step the lane has before the step: the same actions and logp, bit for bit,
+ * as rlks_sample_categorical with those ids followed by rlks_env_step(status = NULL).
+ * Table and node-level envs alike, one launch each: a node-level env (nodes_per_cluster > 0) runs
+ * the sampling form of the node step rlks_env_step would dispatch to, with its
+ * episode log, counters and auto-reset.  reward_dev is the f32 reward, done_dev = terminated,
+ * obs_next_dev the next observation (the next episode's first one on auto-reset).  A lane past the
+ * last table row still gets its action and logp, reward 0, done 0 and no observation.
+ * The env must have autoreset lanes (RLKS_ERR_STATE otherwise); every pointer is required
+ * (RLKS_ERR_ARG).  Asynchronous on `stream` and capturable. */
 int rlks_env_sample_step(rlks_env* env, const float* logits_dev, int explore, int32_t* actions_dev,
                          float* logp_dev, float* obs_next_dev, float* reward_dev, uint8_t* done_dev,
                          void* stream);

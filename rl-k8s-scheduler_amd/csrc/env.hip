@@ -551,6 +551,66 @@ __device__ __forceinline__ bool depart_any(const EnvView& v, const uint32_t* S, 
   return !u_below_S(v, S, P, x.x, lg1p);
 }
 
+// TorchCategorical over the A logits l[0..A): explore -> u = f32(u53(Philox(ctr, key) words 0, 1)) *
+// sum exp(l - max), the first a with u < cumsum; else argmax.  logp of the choice.  Shared by the
+// rollout's fused sample + step and the standalone sampler (oracle.sample_actions restates it).
+__device__ __forceinline__ int categorical(const float* __restrict__ l, int A, bool explore, u32x4 ctr, uint32_t k0,
+                                          uint32_t k1, float& logp) {
+  float mx = l[0];
+  int amax = 0;
+  for (int a = 1; a < A; ++a)
+    if (l[a] > mx) { mx = l[a]; amax = a; }
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) s += expf(l[a] - mx);
+  int act = amax;
+  if (explore) {
+    const u32x4 x = philox4x32_10(ctr, k0, k1);
+    const float u = (float)u53(x.x, x.y) * s;
+    float c = 0.f;
+    act = A - 1;
+    for (int a = 0; a < A; ++a) {
+      c += expf(l[a] - mx);
+      if (u < c) { act = a; break; }
+    }
+  }
+  logp = l[act] - mx - logf(s);
+  return act;
+}
+
+// categorical() over the 2^cs contiguous lanes of a wave that hold one env's (env, cluster) pairs:
+// lane c of the group brings its own logit l (lanes c >= A: any value, never read), every lane of
+// the group returns the same action and logp.  Bit for bit categorical()'s results for logits
+// without NaNs: the maximum is the lowest-index one's own bits, each lane takes one
+// expf(l - mx), and every lane adds the A terms in index order itself (no tree), keeping the
+// running sum at its own index as its CDF entry; the draw is the lowest lane with u < CDF.
+// Called by all 64 lanes of the wave together.
+__device__ __forceinline__ int categorical_lanes(float l, int c, int cs, int A, bool explore, u32x4 ctr, uint32_t k0,
+                                                 uint32_t k1, float& logp) {
+  const int cm = (1 << cs) - 1, base = (int)(threadIdx.x & 63) & ~cm;
+  const unsigned long long gm = cs == 6 ? ~0ull : (1ull << (1 << cs)) - 1ull;  // the group's lanes, from `base`
+  const bool real = c < A;
+  float m = real ? l : -INFINITY;
+  for (int o = 1; o <= cm; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+  const unsigned long long top = (__ballot(real && l == m) >> base) & gm;
+  const int amax = top ? __ffsll(top) - 1 : 0;
+  const float mx = __shfl(l, base + amax);
+  const float e = expf(l - mx);
+  float s = 0.f, cdf = 0.f;
+  for (int a = 0; a < A; ++a) {
+    s += __shfl(e, base + a);
+    cdf = a == c ? s : cdf;
+  }
+  int act = amax;
+  if (explore) {
+    const u32x4 x = philox4x32_10(ctr, k0, k1);
+    const float u = (float)u53(x.x, x.y) * s;
+    const unsigned long long hit = (__ballot(real && u < cdf) >> base) & gm;
+    act = hit ? __ffsll(hit) - 1 : A - 1;
+  }
+  logp = __shfl(l, base + act) - mx - logf(s);
+  return act;
+}
+
 // barrier for LDS traffic only: waits for the workgroup's LDS accesses, not its global stores (a
 // __syncthreads() also waits for every store the wave has in flight)
 __device__ __forceinline__ void lds_barrier() {
@@ -574,14 +634,22 @@ __device__ __forceinline__ void lds_barrier() {
 // Between B and D only LDS is exchanged (lds_barrier), unless an env of the workgroup auto-resets:
 // its clusters' nodes are then rewritten in D by other threads than B's, after a full barrier.
 // A cluster's nodes are touched by one item of B only, so the order of the list does not matter.
-template <int NP, int W>
+// SAMPLE: the actions are drawn here, not read (rlks_env_sample_step): phase S, ahead of A, loads
+// step, episode and each pair's own logit (logits[lane][c], row stride C) and draws the env's
+// action in all of its 2^cs lanes at once (categorical_lanes), so A finds it in a register as it
+// finds a loaded one; the pair lane of cluster 0 writes actions_out and logp, overrun lanes included.
+// Through B the action waits in LDS (s_act) like the step and episode: held in a register it was the
+// 129th (profiles/r10_node_sample/resources.txt).
+template <int NP, int W, bool SAMPLE>
 __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) k_node_step_wl(EnvView v, const double* __restrict__ cost,
                                                       const double* __restrict__ lat,
                                                       const int32_t* __restrict__ actions, float* __restrict__ obs,
                                                       double* __restrict__ rew64, float* __restrict__ rew32,
                                                       uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                                       int32_t* __restrict__ step_out, float* __restrict__ final_obs,
-                                                      int32_t* __restrict__ status, int cs) {
+                                                      int32_t* __restrict__ status, int cs,
+                                                      const float* __restrict__ logits, int explore,
+                                                      int32_t* __restrict__ actions_out, float* __restrict__ logp) {
   if (status && status[0] != 0) return;  // some action was invalid: nothing steps (reference assert, :116)
   constexpr int NT = 64 * W, PB = NP * NT;  // threads, pairs per workgroup
   constexpr uint16_t ARR = 0x8000, DEP = 0x4000;  // list item flags over the pair index
@@ -592,12 +660,36 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
   __shared__ double s_oc[PB], s_ol[PB];        // per pair: obs row t + 1 (0 on reset) cost, latency
   __shared__ double s_rc[PB], s_rl[PB], s_er[PB];  // per env: reward row t cost, latency; running return
   __shared__ int s_n, s_reset;
+  __shared__ int s_act[SAMPLE ? PB : 1];  // per env: the action drawn (D rereads it: no register held through B)
   const int tid = threadIdx.x;
   const int cm = (1 << cs) - 1;
   const int env0 = blockIdx.x * (PB >> cs);
   const int C = v.C, N = v.nodes, D = 3 * C;
-  // ---- A: loads
   int t[NP], ep[NP], a[NP];
+  // ---- S: the draw (the whole wave together: no lane may skip it)
+  if constexpr (SAMPLE) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = tid + j * NT, c = p & cm, lane = env0 + (p >> cs);
+      const bool in = lane < v.N && c < C;
+      float l = 0.f, lp;
+      t[j] = ep[j] = 0;
+      if (in) {
+        t[j] = v.step[lane];
+        ep[j] = v.episode[lane];
+        l = logits[(size_t)lane * C + c];
+      }
+      a[j] = categorical_lanes(l, c, cs, C, explore != 0,
+                               u32x4{(uint32_t)(v.env_offset + lane), (uint32_t)ep[j], (uint32_t)t[j],
+                                     (uint32_t)RLKS_PURPOSE_ACTION << 16},
+                               v.k0, v.k1, lp);
+      if (in && c == 0) {
+        actions_out[lane] = a[j];
+        logp[lane] = lp;
+      }
+    }
+  }
+  // ---- A: loads
   int32_t used0[NP];
   double ocost[NP], olat[NP], rcost[NP], rlat[NP];  // obs row t + 1 (or 0 on reset), reward row t
   double eret[NP];                                  // the chosen cluster's pair: the running return
@@ -605,12 +697,15 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     const int p = tid + j * NT, c = p & cm, lane = env0 + (p >> cs);
-    t[j] = ep[j] = a[j] = used0[j] = 0;
+    if constexpr (!SAMPLE) t[j] = ep[j] = a[j] = 0;
+    used0[j] = 0;
     ocost[j] = olat[j] = rcost[j] = rlat[j] = eret[j] = 0.0;
     if (lane < v.N && c < C) {
-      t[j] = v.step[lane];
-      ep[j] = v.episode[lane];
-      a[j] = actions[lane];
+      if constexpr (!SAMPLE) {
+        t[j] = v.step[lane];
+        ep[j] = v.episode[lane];
+        a[j] = actions[lane];
+      }
       used0[j] = v.used_cpu[(size_t)c * v.N + lane];
       if (t[j] < v.T) {
         const int t1 = t[j] + 1;
@@ -638,6 +733,7 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
         if (c == 0) {
           s_t[el] = t[j];
           s_ep[el] = ep[j];
+          if constexpr (SAMPLE) s_act[el] = a[j];
         }
         s_oc[p] = ocost[j];
         s_ol[p] = olat[j];
@@ -725,7 +821,9 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
       o[C + c] = (float)s_ol[p];
       o[2 * C + c] = __fdiv_rn((float)used, (float)(N * v.cap[c]));
     }
-    if (c == a[j]) {
+    int aj = a[j];
+    if constexpr (SAMPLE) aj = s_act[el];
+    if (c == aj) {
       const int rem = s_rem[el];
       const double r = node_reward_of(v, s_rc[el], s_rl[el], rem);
       v.step[lane] = reset ? 0 : t1;
@@ -747,14 +845,17 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 }
 
 // One lane per env, clusters in turn (C > 64: more clusters than a wave has lanes)
-template <bool LDS_SKIP>
+// (SAMPLE: the lane draws its action from its row of logits before it steps, and writes it and its logp)
+template <bool LDS_SKIP, bool SAMPLE>
 __global__ void __launch_bounds__(256) k_node_step(EnvView v, const double* __restrict__ cost,
                                                    const double* __restrict__ lat,
                                                    const int32_t* __restrict__ actions, float* __restrict__ obs,
                                                    double* __restrict__ rew64, float* __restrict__ rew32,
                                                    uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                                    int32_t* __restrict__ step_out, float* __restrict__ final_obs,
-                                                   int32_t* __restrict__ status) {
+                                                   int32_t* __restrict__ status, const float* __restrict__ logits,
+                                                   int explore, int32_t* __restrict__ actions_out,
+                                                   float* __restrict__ logp) {
   if (status && status[0] != 0) return;  // some action was invalid: nothing steps (reference assert, :116)
   __shared__ uint32_t s_skip[LDS_SKIP ? SKIP_LDS_MAX : 1];
   if (LDS_SKIP) {
@@ -768,7 +869,18 @@ __global__ void __launch_bounds__(256) k_node_step(EnvView v, const double* __re
   NodeCounters k;
   if (lane < v.N) {
     const int t = v.step[lane], ep = v.episode[lane];
-    int a = actions[lane];
+    int a;
+    if constexpr (SAMPLE) {
+      float lp;
+      a = categorical(logits + (size_t)lane * C, C, explore != 0,
+                      u32x4{(uint32_t)(v.env_offset + lane), (uint32_t)ep, (uint32_t)t,
+                            (uint32_t)RLKS_PURPOSE_ACTION << 16},
+                      v.k0, v.k1, lp);
+      actions_out[lane] = a;
+      logp[lane] = lp;
+    } else {
+      a = actions[lane];
+    }
     if (t >= v.T) {  // iloc[t] out of bounds before any change
       over = true;
       if (rew64) rew64[lane] = 0.0;
@@ -820,32 +932,6 @@ __global__ void __launch_bounds__(256) k_node_step(EnvView v, const double* __re
   node_counters_flush(v, k);
   const unsigned long long m = __ballot(over);
   if (status && (threadIdx.x & 63) == 0 && m) atomicAdd(&status[1], (int)__popcll(m));
-}
-
-// TorchCategorical over the A logits l[0..A): explore -> u = f32(u53(Philox(ctr, key) words 0, 1)) *
-// sum exp(l - max), the first a with u < cumsum; else argmax.  logp of the choice.  Shared by the
-// rollout's fused sample + step and the standalone sampler (oracle.sample_actions restates it).
-__device__ __forceinline__ int categorical(const float* __restrict__ l, int A, bool explore, u32x4 ctr, uint32_t k0,
-                                          uint32_t k1, float& logp) {
-  float mx = l[0];
-  int amax = 0;
-  for (int a = 1; a < A; ++a)
-    if (l[a] > mx) { mx = l[a]; amax = a; }
-  float s = 0.f;
-  for (int a = 0; a < A; ++a) s += expf(l[a] - mx);
-  int act = amax;
-  if (explore) {
-    const u32x4 x = philox4x32_10(ctr, k0, k1);
-    const float u = (float)u53(x.x, x.y) * s;
-    float c = 0.f;
-    act = A - 1;
-    for (int a = 0; a < A; ++a) {
-      c += expf(l[a] - mx);
-      if (u < c) { act = a; break; }
-    }
-  }
-  logp = l[act] - mx - logf(s);
-  return act;
 }
 
 // rows i < n: ctr = {ids[3i], ids[3i + 1], ids[3i + 2], ACTION << 16}
@@ -985,6 +1071,34 @@ std::vector<uint32_t> skip32(int pmax, double p) {
     acc = acc * q;
   }
   return out;
+}
+
+// The node step's dispatch, by cluster count and survival-table size; SAMPLE: the
+// forms that draw the actions themselves (rlks_env_sample_step), else the ones that read them.
+template <bool SAMPLE>
+int node_step_launch(rlks_env* e, const int32_t* actions, float* obs, double* rew64, float* rew32, uint8_t* term,
+                     uint8_t* trunc, int32_t* step_out, float* final_obs, int32_t* status, const float* logits,
+                     int explore, int32_t* actions_out, float* logp, hipStream_t s) {
+  const int C = e->cfg.n_clouds;
+  if (C <= NODE_WL_MAX_C) {  // (env, cluster) pairs: 2^cs >= C lanes per env
+    int cs = 0;
+    while ((1 << cs) < C) ++cs;
+    const dim3 gridw(cdiv(e->cfg.n_envs, (NODE_WL_NP * 64 * NODE_WL_W) >> cs)), blkw(64 * NODE_WL_W);
+    hipLaunchKernelGGL((k_node_step_wl<NODE_WL_NP, NODE_WL_W, SAMPLE>), gridw, blkw, 0, s, view(e), e->d_cost, e->d_lat,
+                       actions, obs, rew64, rew32, term, trunc, step_out, final_obs, status, cs, logits, explore,
+                       actions_out, logp);
+    RLKS_LAUNCHED();
+    return RLKS_OK;
+  }
+  const dim3 grid(cdiv(e->cfg.n_envs, 256)), blk(256);
+  if (e->n_skip <= SKIP_LDS_MAX)
+    hipLaunchKernelGGL((k_node_step<true, SAMPLE>), grid, blk, 0, s, view(e), e->d_cost, e->d_lat, actions, obs, rew64,
+                       rew32, term, trunc, step_out, final_obs, status, logits, explore, actions_out, logp);
+  else
+    hipLaunchKernelGGL((k_node_step<false, SAMPLE>), grid, blk, 0, s, view(e), e->d_cost, e->d_lat, actions, obs, rew64,
+                       rew32, term, trunc, step_out, final_obs, status, logits, explore, actions_out, logp);
+  RLKS_LAUNCHED();
+  return RLKS_OK;
 }
 }  // namespace
 
@@ -1174,27 +1288,9 @@ int rlks_env_step(rlks_env* e, const int32_t* actions, float* obs, double* rew64
                        actions, status);
     RLKS_LAUNCHED();
   }
-  if (e->cfg.nodes_per_cluster > 0) {
-    const int C = e->cfg.n_clouds;
-    if (C <= NODE_WL_MAX_C) {  // (env, cluster) pairs: 2^cs >= C lanes per env
-      int cs = 0;
-      while ((1 << cs) < C) ++cs;
-      const dim3 gridw(cdiv(e->cfg.n_envs, (NODE_WL_NP * 64 * NODE_WL_W) >> cs)), blkw(64 * NODE_WL_W);
-      hipLaunchKernelGGL((k_node_step_wl<NODE_WL_NP, NODE_WL_W>), gridw, blkw, 0, s, view(e), e->d_cost, e->d_lat, actions,
-                         obs, rew64, rew32, term, trunc, step_out, final_obs, status, cs);
-      RLKS_LAUNCHED();
-      return RLKS_OK;
-    }
-    const dim3 grid(cdiv(e->cfg.n_envs, 256)), blk(256);
-    if (e->n_skip <= SKIP_LDS_MAX)
-      hipLaunchKernelGGL(k_node_step<true>, grid, blk, 0, s, view(e), e->d_cost, e->d_lat, actions, obs, rew64, rew32,
-                         term, trunc, step_out, final_obs, status);
-    else
-      hipLaunchKernelGGL(k_node_step<false>, grid, blk, 0, s, view(e), e->d_cost, e->d_lat, actions, obs, rew64,
-                         rew32, term, trunc, step_out, final_obs, status);
-    RLKS_LAUNCHED();
-    return RLKS_OK;
-  }
+  if (e->cfg.nodes_per_cluster > 0)
+    return node_step_launch<false>(e, actions, obs, rew64, rew32, term, trunc, step_out, final_obs, status, nullptr, 0,
+                                   nullptr, nullptr, s);
   if (e->cfg.n_clouds == 2 && e->cfg.noise_mode == RLKS_NOISE_PHILOX) {
     hipLaunchKernelGGL(k_env_step2, dim3(grid), dim3(ENV_BLOCK), 0, s, view(e), e->d_cost, e->d_lat, actions, obs,
                        rew64, rew32, term, trunc, step_out, final_obs, status);
@@ -1212,8 +1308,9 @@ int rlks_env_sample_step(rlks_env* e, const float* logits, int explore, int32_t*
   RLKS_REQUIRE(e && logits && actions && logp && obs_next && reward && done, RLKS_ERR_ARG,
                "rlks_env_sample_step: null argument");
   RLKS_REQUIRE(e->cfg.autoreset, RLKS_ERR_STATE, "rlks_env_sample_step: needs autoreset lanes");
-  RLKS_REQUIRE(e->cfg.nodes_per_cluster == 0, RLKS_ERR_UNSUPPORTED,
-               "rlks_env_sample_step: node-level envs step through rlks_env_step");
+  if (e->cfg.nodes_per_cluster > 0)  // f32 reward, done = terminated, trusted (own) actions: no status
+    return node_step_launch<true>(e, nullptr, obs_next, nullptr, reward, done, nullptr, nullptr, nullptr, nullptr, logits,
+                                  explore, actions, logp, (hipStream_t)stream);
   hipLaunchKernelGGL(k_sample_step, dim3(cdiv(e->cfg.n_envs, ENV_BLOCK)), dim3(ENV_BLOCK), table_lds(e),
                      (hipStream_t)stream, view(e), e->d_cost, e->d_lat, logits, explore, actions, logp,
                      obs_next, reward, done);

@@ -769,9 +769,9 @@ static int check_desc(const rlks_mlp_desc* d) {
 }
 
 // Node-level envs (nodes_per_cluster > 0): the node sweep has its own workgroup shape (k_node_step:
-// 64 envs x W waves), so a rollout step is three launches on the stream: forward of both nets on
-// obs[t] (logits[t], values[t]) -> Categorical sample (actions[t], logp[t]) -> trusted env step
-// (obs[t + 1], f32 rewards[t], dones[t]); then the bootstrap V(obs[T]).  `w` = the split-fp16
+// 64 envs x W waves), so a rollout step is two launches on the stream: forward of both nets on
+// obs[t] (logits[t], values[t]) -> the sampling node step (rlks_env_sample_step: actions[t], logp[t],
+// obs[t + 1], f32 rewards[t], dones[t]); then the bootstrap V(obs[T]).  `w` = the split-fp16
 // weights (SF16) or nullptr (fp32 kernels).
 static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
                         int explore, const SfWs* w, hipStream_t s) {
@@ -805,13 +805,11 @@ static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* para
     }
     return RLKS_OK;
   };
-  const EnvView v = view(env);
   for (int t = 0; t < b->T; ++t) {
     const size_t tN = (size_t)t * N;
     if (int rc = forward(b->obs + tN * D, b->logits + tN * A, b->values + tN)) return rc;
-    if (int rc = launch_sample(v, b->logits + tN * A, A, explore, b->actions + tN, b->logp + tN, s)) return rc;
-    if (int rc = rlks_env_step(env, b->actions + tN, b->obs + (tN + N) * D, nullptr, b->rewards + tN, b->dones + tN,
-                               nullptr, nullptr, nullptr, nullptr, s))
+    if (int rc = rlks_env_sample_step(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN,
+                                      b->obs + (tN + N) * D, b->rewards + tN, b->dones + tN, s))
       return rc;
   }
   return forward(b->obs + (size_t)b->T * N * D, nullptr, b->values + (size_t)b->T * N);

@@ -18,7 +18,6 @@ struct WideWs {
   float* dzb;  // [M][H] dZ1 (dZ2 goes straight to the dzh / dzl planes)
   _Float16 *dzh, *dzl;  // dZ2 planes [M][H]
   _Float16 *xh, *xl;    // X planes [M][D] (obs_dim D a multiple of 32)
-  double* rew64;     // [M] env-step scratch (rollout)
   float* part;       // split-K / split column-sum partials of the weight gradients
   unsigned* stat_slots;
   int64_t bytes;

@@ -59,7 +59,6 @@ WideWs wide_ws_layout(int D, int H, int A, int M, char* base) {
   w.dzl = (_Float16*)take(2LL * Mp * H);
   w.xh = (_Float16*)take(2LL * Mp * D);  // rows [M, Mp) zeroed by wide_grad (dW1's K runs over Mp)
   w.xl = (_Float16*)take(2LL * Mp * D);
-  w.rew64 = (double*)take(8LL * M);
   {  // weight-gradient partials: dW3 [A][H], dW2 [H][H], dW1 [H][D] (K = M), column sums of M rows
     int64_t pf = (int64_t)2 * colsum_splits(M) * H;  // (hi, lo planes)
     pf = std::max(pf, (int64_t)gemm_splits(A, H, M) * A * H);
@@ -725,10 +724,17 @@ int wide_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, con
     const float* obs = b->obs + (size_t)t * N * D;
     if (int rc = wide_forward(d, params, obs, D, N, w, b->logits + (size_t)t * N * A, b->values + (size_t)t * N, s))
       return rc;
+    if (v.nodes > 0) {  // node-level env: Categorical sample + step in one launch (the sampling node step)
+      if (int rc = rlks_env_sample_step(env, b->logits + (size_t)t * N * A, explore, b->actions + (size_t)t * N,
+                                        b->logp + (size_t)t * N, b->obs + (size_t)(t + 1) * N * D,
+                                        b->rewards + (size_t)t * N, b->dones + (size_t)t * N, s))
+        return rc;
+      continue;
+    }
     if (int rc = launch_sample(v, b->logits + (size_t)t * N * A, A, explore, b->actions + (size_t)t * N,
                                b->logp + (size_t)t * N, s))
       return rc;
-    if (int rc = rlks_env_step(env, b->actions + (size_t)t * N, b->obs + (size_t)(t + 1) * N * D, w.rew64,
+    if (int rc = rlks_env_step(env, b->actions + (size_t)t * N, b->obs + (size_t)(t + 1) * N * D, nullptr,
                                b->rewards + (size_t)t * N, b->dones + (size_t)t * N, nullptr, nullptr, nullptr, nullptr,
                                s))
       return rc;

@@ -463,6 +463,27 @@ class VecK8sMultiCloudEnv:
                                                                          "final_observation": self.final_obs,
                                                                          "status": self._status}
 
+    def sample_step(self, logits, explore=True):
+        """Categorical sample (explore) or argmax of `logits` [N, C], then the env step, in one kernel
+        launch (rlks_env_sample_step), for table and node-level envs alike.
+        -> (actions int32 [N], logp f32 [N], obs [N, 3C], reward f32 [N], done u8 [N]): device
+        tensors owned by the env, as step()'s.  Lane i draws from the Philox counter (env_offset + i,
+        its episode, its step) under the env's seed.  Needs autoreset lanes (RlksError otherwise)."""
+        torch = _torch()
+        lg = torch.as_tensor(logits, device=self.device).to(torch.float32).contiguous()
+        if tuple(lg.shape) != (self.num_envs, self.n_clouds):
+            raise ValueError(f"sample_step: logits must be [{self.num_envs}, {self.n_clouds}], got {list(lg.shape)}")
+        if not hasattr(self, "_s_actions"):
+            N = self.num_envs
+            self._s_actions = torch.zeros(N, dtype=torch.int32, device=self.device)
+            self._s_logp = torch.zeros(N, dtype=torch.float32, device=self.device)
+            self._s_reward = torch.zeros(N, dtype=torch.float32, device=self.device)
+            self._s_done = torch.zeros(N, dtype=torch.uint8, device=self.device)
+        _lib.call("rlks_env_sample_step", self.handle, _lib.ptr(lg), int(bool(explore)), _lib.ptr(self._s_actions),
+                  _lib.ptr(self._s_logp), _lib.ptr(self.obs), _lib.ptr(self._s_reward), _lib.ptr(self._s_done),
+                  self.dev.stream)
+        return self._s_actions, self._s_logp, self.obs, self._s_reward, self._s_done
+
     def check_status(self):
         """raise the reference's exceptions for the last step (synchronises)"""
         st = self._status.cpu().numpy()
