@@ -111,6 +111,29 @@ int rlks_env_sample_step(rlks_env* env, const float* logits_dev, int explore, in
                          float* logp_dev, float* obs_next_dev, float* reward_dev, uint8_t* done_dev,
                          void* stream);
 
+/* Baseline schedulers: actions_dev[lane] = the cluster rule `rule` (RLKS_RULE_*)
+ * picks for each lane from what a scheduler sees before the step: the lane's observation row
+ * obs_dev[lane][3 n_clouds] = [cost, lat, util] (normally the env's current observation), its step
+ * and episode counters, the env's constants and, on a node-level env, its clusters' used millicores.
+ *   ROUND_ROBIN       step % C
+ *   CHEAPEST          lowest index of the minimum f32 obs[c]
+ *   MYOPIC            lowest index of the maximum (strict >) of s_c = w_cost * (double)obs[c] +
+ *                     w_lat * (double)obs[C + c], in f64 with the products and the sum rounded separately:
+ *                     the cluster of the largest immediate reward, as far as the f32 observation shows it
+ *   LEAST_LOADED      lowest index of the minimum f32 obs[2C + c]
+ *   MYOPIC_WITH_ROOM  MYOPIC over the clusters that can take one more pod, used_cpu[c] / pod_cpu_m <
+ *                     nodes_per_cluster * min(node_cpu[c] / pod_cpu_m, node_mem[c] / pod_mem_mi) in integers
+ *                     (a cluster's nodes are equally sized: some node has room); over all clusters when
+ *                     none has room; on a table env every cluster has room
+ *   RANDOM            the action rlks_sample_categorical draws from an all-zero logits row with ids
+ *                     {env_offset + lane, episode, step} under the env's seed.  This is
+ *                     rlks_env_sample_step's counter: a lane must not use both for the same step, or
+ *                     the two draws are one.
+ * All rules are exact.  A lane past the last table row is decided like any other.  Table and node-level
+ * envs, any n_clouds, with or without autoreset.  One launch, asynchronous on `stream` and capturable:
+ * no validation launch, no host read.  A NULL pointer or an unknown rule: RLKS_ERR_ARG. */
+int rlks_env_rule_actions(rlks_env* env, int rule, const float* obs_dev, int32_t* actions_dev, void* stream);
+
 /* TorchCategorical sample (explore != 0) or argmax of rows i < n of logits_dev[n][A]: the draw of
  * row i is Philox4x32-10 of the counter {ids[3i], ids[3i + 1], ids[3i + 2], RLKS_PURPOSE_ACTION << 16}
  * under key = seed, turned into an action exactly as rlks_env_sample_step does (ids may be NULL

@@ -36,6 +36,18 @@ enum {
   RLKS_PURPOSE_OCCUPANCY = 5
 };
 
+/* Baseline schedulers of rlks_env_rule_actions: one decision per lane from its
+ * observation row [cost[C], lat[C], util[C]], its step and episode and, on node-level envs, its
+ * clusters' used millicores.  Ties go to the lowest index. */
+enum {
+  RLKS_RULE_ROUND_ROBIN = 0,      /* step % C (train_and_compare.py:65 at C = 2) */
+  RLKS_RULE_CHEAPEST = 1,         /* argmin of the f32 cost (normal_scheduler_step, :156-157, at C = 2) */
+  RLKS_RULE_MYOPIC = 2,           /* argmax of w_cost * cost + w_lat * lat in f64: the immediate reward */
+  RLKS_RULE_LEAST_LOADED = 3,     /* argmin of the f32 utilisation */
+  RLKS_RULE_MYOPIC_WITH_ROOM = 4, /* MYOPIC over the clusters with room for one more pod (all, if none has) */
+  RLKS_RULE_RANDOM = 5            /* uniform: rlks_sample_categorical's draw from all-zero logits */
+};
+
 typedef struct rlks_env_cfg {
   int32_t n_envs;        /* lanes */
   int32_t n_rows;        /* T: table rows (reference: 100, normalized_rl_data.csv) */

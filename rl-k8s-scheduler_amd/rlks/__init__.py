@@ -5,6 +5,8 @@ Public surface (mirrors the reference's gymnasium env and RLlib PPO call sites):
     PPO, PPOConfig                             rlks.ppo   (train_ppo.py:9-31, eval_ppo.py:17-27)
     evaluate, round_robin_baseline             rlks.evaluation (final_evaluation.py:39-82,
                                                                train_and_compare.py:53-79)
+    evaluate_nodes, comparison_report          rlks.evaluation (the same for node-level envs and any number of
+                                                               policies and device baselines)
     build_reference_table, synthetic_table     rlks.tables (generate_real_pricing.py, normalize_data.py)
     latest_checkpoint, run_experiment          rlks.checkpoints (final_evaluation.py:13-25, train_final.py:22-35)
     JsonLinesReporter                          rlks.metrics (train_ppo.py:29-30 per-iteration report)
@@ -26,7 +28,8 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
         from . import ppo
 
         return getattr(ppo, name)
-    if name in ("evaluate", "round_robin_baseline", "EvalResult"):
+    if name in ("evaluate", "round_robin_baseline", "EvalResult", "evaluate_nodes", "NodeEvalResult",
+                "comparison_report"):
         from . import evaluation
 
         return getattr(evaluation, name)

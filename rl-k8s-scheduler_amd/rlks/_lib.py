@@ -26,6 +26,12 @@ RLKS_PRECISION_FP32, RLKS_PRECISION_SF16, RLKS_PRECISION_WIDE, RLKS_PRECISION_F1
 RLKS_STAT_POLICY_LOSS, RLKS_STAT_VF_LOSS, RLKS_STAT_KL, RLKS_STAT_ENTROPY, RLKS_STAT_ROWS = 0, 1, 2, 3, 4
 RLKS_STAT_GRAD_GNORM = 5
 RLKS_EPLOG_CAP = 128
+(RLKS_RULE_ROUND_ROBIN, RLKS_RULE_CHEAPEST, RLKS_RULE_MYOPIC, RLKS_RULE_LEAST_LOADED, RLKS_RULE_MYOPIC_WITH_ROOM,
+ RLKS_RULE_RANDOM) = range(6)
+# rule names of the Python surface (VecK8sMultiCloudEnv.rule_actions, rlks.evaluation) -> RLKS_RULE_*
+RULES = {"round_robin": RLKS_RULE_ROUND_ROBIN, "cheapest": RLKS_RULE_CHEAPEST, "myopic": RLKS_RULE_MYOPIC,
+         "least_loaded": RLKS_RULE_LEAST_LOADED, "myopic_with_room": RLKS_RULE_MYOPIC_WITH_ROOM,
+         "random": RLKS_RULE_RANDOM}
 
 
 class EnvCfg(C.Structure):
@@ -100,6 +106,7 @@ SIGNATURES = {
     "rlks_env_reset": [_P, _P, _P, _P],
     "rlks_env_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rlks_env_sample_step": [_P, _P, _I, _P, _P, _P, _P, _P, _P],
+    "rlks_env_rule_actions": [_P, _I, _P, _P, _P],
     "rlks_env_episode_stats": [_P, _P, _I, _P],
     "rlks_env_lane_state": [_P, _P, _P, _P],
     "rlks_env_episode_log": [_P, _P, _P, _P, _I, _P],

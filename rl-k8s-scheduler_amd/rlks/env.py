@@ -484,6 +484,26 @@ class VecK8sMultiCloudEnv:
                   self.dev.stream)
         return self._s_actions, self._s_logp, self.obs, self._s_reward, self._s_done
 
+    def rule_actions(self, rule, obs=None):
+        """One baseline-scheduler decision per lane on the device (rlks_env_rule_actions, DESIGN.md
+        §19) -> actions int32 [N], a device tensor owned by the env (overwritten by the next call).
+        `rule`: "round_robin", "cheapest", "myopic", "least_loaded", "myopic_with_room", "random" or
+        the RLKS_RULE_* value; `obs` [N, 3C] float32 defaults to the env's current observation.
+        "random" draws from the Philox counter sample_step() uses: do not mix the two on one step."""
+        torch = _torch()
+        if isinstance(rule, str):
+            if rule not in _lib.RULES:
+                raise ValueError(f"unknown rule {rule!r}; one of {sorted(_lib.RULES)}")
+            rule = _lib.RULES[rule]
+        o = self.obs if obs is None else torch.as_tensor(obs, device=self.device).to(torch.float32).contiguous()
+        if tuple(o.shape) != (self.num_envs, self.obs_dim):
+            raise ValueError(f"rule_actions: obs must be [{self.num_envs}, {self.obs_dim}], got {list(o.shape)}")
+        if not hasattr(self, "_r_actions"):
+            self._r_actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.call("rlks_env_rule_actions", self.handle, int(rule), _lib.ptr(o), _lib.ptr(self._r_actions),
+                  self.dev.stream)
+        return self._r_actions
+
     def check_status(self):
         """raise the reference's exceptions for the last step (synchronises)"""
         st = self._status.cpu().numpy()

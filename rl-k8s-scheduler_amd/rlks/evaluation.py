@@ -15,6 +15,12 @@ observation: reset + 99 steps), so lane e sees exactly the cpu-load draws episod
 reference's sequential loop sees.  Episode returns accumulate in float64 in step order from 0.0,
 as `ep_reward += reward` does, so rewards, choices and costs equal the sequential loop's bit for bit
 (tests/test_gpu_eval.py checks this against the drop-in env driven step by step).
+
+Baselines beyond the reference's two, and node-level envs: the rule names of
+rlks._lib.RULES are decided on the device by rlks_env_rule_actions, one launch ahead of the step, so a
+baseline's loop is as device-resident as a policy's.  evaluate_nodes() is the harness for node-level
+envs (returns, choices, placed / rejected / departed pods, utilisation); comparison_report() prints
+policies and baselines side by side, as train_and_compare.py:75-79 and final_evaluation.py:73-74 do.
 """
 from __future__ import annotations
 
@@ -90,7 +96,11 @@ def _params_of(policy):
 def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=None,
              baseline_cost: float = BASELINE_COST) -> EvalResult:
     """final_evaluation.py:39-77 batched: `policy` is a PPO algorithm / PolicyParams (greedy argmax,
-    compute_single_action(obs, explore=False)), or "round_robin" / "greedy" for the baselines.
+    compute_single_action(obs, explore=False)), or "round_robin" / "greedy" for the baselines, or a
+    device rule (VecK8sMultiCloudEnv.rule_actions): "cheapest" (= "greedy"), "myopic" (the largest
+    immediate reward: the optimal policy of the table env, whose reward depends on nothing the agent
+    changes), "least_loaded", "myopic_with_room" (= "myopic" here: a table env always has room) and
+    "random" (Philox draws keyed by `seed`).
 
     seed: the value of the reference's `random.seed(seed)` before its first episode (its env is
     unseeded, so the process-global stream decides; None draws one from this process's `random`)."""
@@ -100,7 +110,7 @@ def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=N
         raise ValueError("num_episodes must be positive")
     table = table if table is not None else load_table()
     if isinstance(policy, str):
-        if policy not in ("round_robin", "greedy"):
+        if policy not in ("round_robin", "greedy") and policy not in _lib.RULES:
             raise ValueError(f"unknown baseline policy {policy!r}")
         params = None
     else:
@@ -113,7 +123,10 @@ def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=N
         device = params.flat.device if params is not None else torch.device("cuda", torch.cuda.current_device())
     E = int(num_episodes)
     T = table.n_rows - 1  # max_steps (:66): every episode is exactly 99 steps
-    env = VecK8sMultiCloudEnv(E, table=table, noise="mt19937", autoreset=False, device=device)
+    rule = policy if isinstance(policy, str) and policy not in ("round_robin", "greedy") else None
+    # (the env's own seed keys only the "random" rule's Philox draws: the MT19937 lanes are seeded below)
+    env = VecK8sMultiCloudEnv(E, table=table, noise="mt19937", autoreset=False, device=device,
+                              seed=int(seed) if rule == "random" else 0)
     try:
         env.seed([int(seed)] * E)
         per_episode = DRAWS_PER_OBS * (T + 1)
@@ -128,6 +141,8 @@ def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=N
             if params is not None:
                 params.forward(obs, logits, values)
                 a = torch.argmax(logits, dim=1).to(torch.int32)   # np.argmax: first maximum
+            elif rule is not None:                               # rlks_env_rule_actions, on the device
+                a = env.rule_actions(rule)
             elif policy == "round_robin":                        # train_and_compare.py:65
                 a = torch.full((E,), t % 2, dtype=torch.int32, device=env.device)
             else:                                                # normal_scheduler_step (:156-157)
@@ -172,6 +187,118 @@ def evaluate_lanes(params, num_episodes: int, *, table=None, nodes=None, seed=0,
         return ret.cpu().numpy()
     finally:
         env.close()
+
+
+@dataclass
+class NodeEvalResult:
+    """evaluate_nodes(): one episode per lane of a node-level env"""
+    rewards: np.ndarray      # float64 [episodes], step rewards summed in step order
+    actions: np.ndarray      # int32 [steps, episodes]
+    choices: np.ndarray      # int64 [C]: decisions per cluster (sums to steps * episodes)
+    placed: int              # pods placed, rejected (no node of the chosen cluster had room), departed
+    rejected: int
+    departed: int
+    mean_util: np.ndarray    # float64 [C]: mean cpu utilisation observed after each step, over steps and lanes
+    extra: dict = field(default_factory=dict)
+
+    @property
+    def rejection_rate(self) -> float:
+        """rejected / arrived pods (0 when none arrived)"""
+        n = self.placed + self.rejected
+        return self.rejected / n if n else 0.0
+
+
+def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, device=None) -> NodeEvalResult:
+    """`num_episodes` episodes of a node-level env (rlks.env.NodeSpec `nodes`), one lane each, every lane
+    stepped by the same launches: episode e runs on lane e of a Philox env keyed by `seed`, with
+    autoreset=False, for max_steps steps.  `policy`: a PPO algorithm or PolicyParams (greedy argmax, as
+    evaluate_lanes and RLlib's evaluation workers, explore=False) or a rule name of rlks._lib.RULES
+    (decided on the device by rlks_env_rule_actions).  Returns are summed in float64 in step order,
+    as evaluate_lanes sums them; the pod counts are rlks_env_counters'.  The loop stays on the device:
+    everything is read back once at the end.
+
+    The comparison of two policies is paired: arrivals are keyed by (lane, episode, step), not by what
+    was decided, so two calls with the same `seed` and episode count see the same arrival counts at
+    every step (placed + rejected is the same), and the same initial occupancy; only placements, and
+    with them the departures, differ."""
+    import torch
+
+    if num_episodes <= 0:
+        raise ValueError("num_episodes must be positive")
+    if nodes is None:
+        raise ValueError("evaluate_nodes needs a NodeSpec; table envs are evaluate()'s")
+    table = table if table is not None else load_table()
+    C_ = table.n_clouds
+    if isinstance(policy, str):
+        if policy not in _lib.RULES:
+            raise ValueError(f"unknown baseline policy {policy!r}; one of {sorted(_lib.RULES)}")
+        params = None
+    else:
+        params = _params_of(policy)
+        if params.D != 3 * C_ or params.A != C_:
+            raise ValueError("policy shape does not match the table's clouds")
+        if device is None:
+            device = params.flat.device
+    E = int(num_episodes)
+    env = VecK8sMultiCloudEnv(E, table=table, seed=int(seed), noise="philox", autoreset=False, device=device,
+                              nodes=nodes)
+    try:
+        T = env.max_steps
+        env.counters(enable=1)
+        obs = env.reset()
+        ret = torch.zeros(E, dtype=torch.float64, device=env.device)
+        util = torch.zeros(E, C_, dtype=torch.float64, device=env.device)
+        actions = torch.empty(T, E, dtype=torch.int32, device=env.device)
+        if params is not None:
+            logits = torch.empty(E, C_, dtype=torch.float32, device=env.device)
+            values = torch.empty(E, dtype=torch.float32, device=env.device)
+        for t in range(T):
+            if params is not None:
+                params.forward(obs, logits, values)
+                a = torch.argmax(logits, dim=1).to(torch.int32)
+            else:
+                a = env.rule_actions(policy)
+            actions[t] = a
+            obs, r, term, _, _ = env.step(a)
+            ret += r
+            util += obs[:, 2 * C_:]
+        counters = env.counters()
+        env.check_status()
+        if not bool(term.all()):
+            raise RuntimeError("evaluation lanes did not terminate after max_steps")
+        acts = actions.cpu().numpy()
+        k = counters.cpu().numpy()
+        return NodeEvalResult(ret.cpu().numpy(), acts, np.bincount(acts.reshape(-1), minlength=C_).astype(np.int64),
+                              int(k[1]), int(k[2]), int(k[3]), util.sum(0).cpu().numpy() / (T * E),
+                              {"seed": int(seed)})
+    finally:
+        env.close()
+
+
+def comparison_report(results: dict, baseline: str | None = None) -> str:
+    """One line per policy of `results` (name -> EvalResult or NodeEvalResult): mean return,
+    improvement over `baseline` (a key of results; default: the first) in percent of its mean return,
+    rejection rate (node-level results) and the share of decisions each cluster got -- the "RL vs
+    baseline" table of train_and_compare.py:75-79 and the "improvement vs the greedy baseline" of
+    final_evaluation.py:73-74 for any number of policies."""
+    if not results:
+        raise ValueError("comparison_report needs at least one result")
+    baseline = next(iter(results)) if baseline is None else baseline
+    if baseline not in results:
+        raise ValueError(f"baseline {baseline!r} is not among the results {list(results)}")
+    base = float(np.mean(results[baseline].rewards))
+    width = max(len(str(n)) for n in results)
+    lines = []
+    for name, res in results.items():
+        mean = float(np.mean(res.rewards))
+        ch = res.choices
+        counts = np.array(list(ch.values()) if isinstance(ch, dict) else ch, np.float64)
+        shares = " ".join(f"{x:.1%}" for x in counts / max(counts.sum(), 1.0))
+        imp = 100.0 * (mean - base) / abs(base) if base else float("nan")
+        rej = f"{res.rejection_rate:7.2%}" if hasattr(res, "rejection_rate") else "    n/a"
+        lines.append(f"{str(name):<{width}} : return = {mean:10.2f} | vs {baseline} = {imp:+7.2f}% | "
+                     f"rejected = {rej} | choices = {shares}")
+    return "\n".join(lines)
 
 
 def round_robin_baseline(num_episodes: int = 5, **kw) -> np.ndarray:

@@ -44,6 +44,19 @@ from .schedules import schedule_value, validate_grad_clip, validate_schedule
 from .tables import load_table
 
 
+def validate_baselines(names):
+    """evaluation_baselines as a list of rule names (rlks._lib.RULES), or None"""
+    if names is None:
+        return None
+    if isinstance(names, str):
+        names = [names]
+    names = [str(n) for n in names]
+    bad = [n for n in names if n not in _lib.RULES]
+    if bad:
+        raise ValueError(f"unknown evaluation baseline(s) {bad}; one of {sorted(_lib.RULES)}")
+    return names
+
+
 class PPOConfig:
     """RLlib-style builder.  Defaults are RLlib's old-API-stack PPOConfig defaults."""
 
@@ -83,6 +96,9 @@ class PPOConfig:
         self.explore = True
         self.evaluation_interval = None
         self.evaluation_duration = 10
+        # rule names (rlks._lib.RULES) evaluated beside the policy each time train() evaluates, with
+        # its seed and lane count: result["evaluation"]["baselines"][name]; None = none
+        self.evaluation_baselines = None
         self.metrics_num_episodes_for_smoothing = 100
         # rlks.metrics.JsonLinesReporter: append every train() result to this file as one JSON line
         # (also: $RLKS_METRICS_JSONL)
@@ -163,11 +179,13 @@ class PPOConfig:
             self.num_gpus = num_gpus
         return self
 
-    def evaluation(self, evaluation_interval=None, evaluation_duration=None, **kw):
+    def evaluation(self, evaluation_interval=None, evaluation_duration=None, evaluation_baselines=None, **kw):
         if evaluation_interval is not None:
             self.evaluation_interval = evaluation_interval
         if evaluation_duration is not None:
             self.evaluation_duration = evaluation_duration
+        if evaluation_baselines is not None:
+            self.evaluation_baselines = validate_baselines(evaluation_baselines)
         return self
 
     def reporting(self, metrics_num_episodes_for_smoothing=None, json_lines=None, **kw):
@@ -213,6 +231,8 @@ class PPOConfig:
                 c.adam_betas = tuple(v)
             elif k == "nodes":
                 c.nodes = NodeSpec.from_dict(v) if v is not None else None
+            elif k == "evaluation_baselines":
+                c.evaluation_baselines = validate_baselines(v)
             elif k != "env" and hasattr(c, k):
                 setattr(c, k, v)
         return c
@@ -253,6 +273,7 @@ class PPO:
         for name in ("lr_schedule", "entropy_coeff_schedule"):
             if getattr(cfg, name) is not None:
                 validate_schedule(getattr(cfg, name), name)
+        validate_baselines(cfg.evaluation_baselines)
         self.torch = torch
         self.rank, self.world = ddp.rank_world()
         self.multi = self.world > 1 or ddp.forced()  # the multi-rank SGD step (ddp.forced: one rank, RCCL)
@@ -616,14 +637,29 @@ class PPO:
     def evaluate(self, episodes=None):
         """greedy evaluation (RLlib evaluation workers, explore=False): `episodes` episodes, one
         lane each (train_final.py:19 .evaluation(evaluation_interval=5, evaluation_duration=20))"""
-        from .evaluation import evaluate_lanes
+        from .evaluation import evaluate as evaluate_table
+        from .evaluation import evaluate_lanes, evaluate_nodes
 
         n = int(episodes or self.config.evaluation_duration)
-        rets = evaluate_lanes(self.params, n, table=self.table, nodes=self.config.nodes,
-                              seed=(self.seed * 7919 + self.iteration) & 0xFFFFFFFF, device=self.device)
-        return {"episode_reward_mean": float(np.mean(rets)), "episode_reward_min": float(np.min(rets)),
-                "episode_reward_max": float(np.max(rets)), "episodes_this_iter": n,
-                "episode_len_mean": float(self.table.n_rows - 1)}
+        seed = (self.seed * 7919 + self.iteration) & 0xFFFFFFFF
+        rets = evaluate_lanes(self.params, n, table=self.table, nodes=self.config.nodes, seed=seed, device=self.device)
+        out = {"episode_reward_mean": float(np.mean(rets)), "episode_reward_min": float(np.min(rets)),
+               "episode_reward_max": float(np.max(rets)), "episodes_this_iter": n,
+               "episode_len_mean": float(self.table.n_rows - 1)}
+        names = validate_baselines(self.config.evaluation_baselines)
+        if names:
+            # the same seed and lane count as the policy's evaluation above: on a node-level env the
+            # baselines then meet the policy's arrivals (evaluate_nodes: a paired comparison)
+            base = {}
+            for name in names:
+                if self.config.nodes is not None:
+                    r = evaluate_nodes(name, n, nodes=self.config.nodes, table=self.table, seed=seed, device=self.device)
+                    base[name] = {"episode_reward_mean": float(np.mean(r.rewards)), "rejection_rate": r.rejection_rate}
+                else:
+                    r = evaluate_table(name, n, seed=seed, table=self.table, device=self.device)
+                    base[name] = {"episode_reward_mean": float(np.mean(r.rewards))}
+            out["baselines"] = base
+        return out
 
     def train(self):
         t0 = time.time()
