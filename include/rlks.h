@@ -434,6 +434,26 @@ int rlks_ppo_adam_apply_clip(const rlks_mlp_desc* desc, float* params_dev, float
 /* RLlib update_kl: kl = stats_sum[0] / stats_sum[1]; x1.5 if kl > 2*target, x0.5 if < target/2 */
 int rlks_kl_update(float* dyn_dev, const double* kl_sum_count_dev, float kl_target, void* stream);
 
+/* ============================================================== rollout metrics =========== */
+/* What the policy did during one rollout, reduced on the device (PPOConfig.reporting(rollout_metrics=True),
+ * DESIGN.md §20): out_dev = double[RLKS_RM_FIXED + A + C], the RLKS_RM_* slots of rlks_types.h, then A
+ * action counts, then C sums of the utilisation columns obs[t][n][2C + c] (t < T; D = the obs row
+ * length, D >= 3 C).  Reads bufs->actions / rewards / dones / vtarg, values[0..T) and those obs columns;
+ * adv, logits and logp are not read.  vtarg must be valid: call it after rlks_gae.
+ * Arithmetic: every f32 input is widened to f64 first, squares and the residual are formed in f64, all
+ * sums are f64, min / max are taken on the f32 values.  Order: stage one writes one partial record per
+ * workgroup of a bounded grid into the workspace (sample -> workgroup, wave and lane is a function of
+ * T N alone; lanes meet by cross-lane butterflies, waves in index order), stage two sums the records in
+ * index order.  No floating-point atomics: the same inputs give the same bits on every run.
+ * rlks_rollout_metrics_size: the doubles in out_dev (negative RLKS_ERR_* for bad A / C).  The workspace
+ * is rlks_rollout_metrics_workspace_bytes(T, N, A, C) bytes, 8-byte aligned, and holds nothing between
+ * calls.  A <= 4096, C <= 1024 (RLKS_ERR_UNSUPPORTED beyond).  Two launches, asynchronous on `stream`
+ * and capturable. */
+int rlks_rollout_metrics_size(int A, int C);
+int rlks_rollout_metrics_workspace_bytes(int T, int N, int A, int C, int64_t* bytes);
+int rlks_rollout_metrics(const rlks_rollout_bufs* bufs, int D, int A, int C, double* out_dev,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,24 @@ enum {
   RLKS_STAT_SIZE = 8
 };
 
+/* Per-iteration rollout metrics record written by rlks_rollout_metrics (double[RLKS_RM_FIXED + A + C],
+ * DESIGN.md §20): sums are f64 sums of the f32 inputs widened first, min / max are taken on the f32
+ * values, counts are exact integers held in doubles.  After the fixed slots: A action counts, then the C
+ * sums of the utilisation columns obs[t][n][2C + c], t < T. */
+enum {
+  RLKS_RM_ROWS = 0,        /* samples read = T N */
+  RLKS_RM_REWARD_SUM = 1,
+  RLKS_RM_REWARD_MIN = 2,
+  RLKS_RM_REWARD_MAX = 3,
+  RLKS_RM_DONES = 4,       /* steps with a non-zero done byte */
+  RLKS_RM_VALUE_SUM = 5,   /* values[0..T) */
+  RLKS_RM_VTARG_SUM = 6,
+  RLKS_RM_VTARG_SQ = 7,
+  RLKS_RM_RESID_SUM = 8,   /* resid = (double)vtarg - (double)values */
+  RLKS_RM_RESID_SQ = 9,
+  RLKS_RM_FIXED = 10
+};
+
 #ifdef __cplusplus
 }
 #endif

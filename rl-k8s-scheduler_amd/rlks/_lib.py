@@ -26,6 +26,9 @@ RLKS_PRECISION_FP32, RLKS_PRECISION_SF16, RLKS_PRECISION_WIDE, RLKS_PRECISION_F1
 RLKS_STAT_POLICY_LOSS, RLKS_STAT_VF_LOSS, RLKS_STAT_KL, RLKS_STAT_ENTROPY, RLKS_STAT_ROWS = 0, 1, 2, 3, 4
 RLKS_STAT_GRAD_GNORM = 5
 RLKS_EPLOG_CAP = 128
+# rlks_rollout_metrics record slots (include/rlks_types.h RLKS_RM_*)
+(RLKS_RM_ROWS, RLKS_RM_REWARD_SUM, RLKS_RM_REWARD_MIN, RLKS_RM_REWARD_MAX, RLKS_RM_DONES, RLKS_RM_VALUE_SUM,
+ RLKS_RM_VTARG_SUM, RLKS_RM_VTARG_SQ, RLKS_RM_RESID_SUM, RLKS_RM_RESID_SQ, RLKS_RM_FIXED) = range(11)
 (RLKS_RULE_ROUND_ROBIN, RLKS_RULE_CHEAPEST, RLKS_RULE_MYOPIC, RLKS_RULE_LEAST_LOADED, RLKS_RULE_MYOPIC_WITH_ROOM,
  RLKS_RULE_RANDOM) = range(6)
 # rule names of the Python surface (VecK8sMultiCloudEnv.rule_actions, rlks.evaluation) -> RLKS_RULE_*
@@ -155,6 +158,9 @@ SIGNATURES = {
     "rlks_ppo_adam_apply_clip": [C.POINTER(MlpDesc), _P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _F, _P, _P, _I64, _I,
                                  _P],
     "rlks_kl_update": [_P, _P, _F, _P],
+    "rlks_rollout_metrics_size": [_I, _I],
+    "rlks_rollout_metrics_workspace_bytes": [_I, _I, _I, _I, C.POINTER(_I64)],
+    "rlks_rollout_metrics": [C.POINTER(RolloutBufs), _I, _I, _I, _P, _P, _I64, _P],
 }
 _RESTYPES = {"rlks_last_error": C.c_char_p, "rlks_version": C.c_char_p}
 

@@ -63,6 +63,8 @@ class JsonLinesReporter:
         out["learner"] = learner
         if "evaluation" in result:
             out["evaluation"] = result["evaluation"]
+        if "custom_metrics" in result:  # PPOConfig.reporting(rollout_metrics=True), under RLlib's key
+            out["custom_metrics"] = result["custom_metrics"]
         if algo is not None:
             t = result.get("time_this_iter_s") or float("nan")
             steps = algo.samples * algo.world

@@ -15,6 +15,7 @@ the torch-CPU oracle under oracle/, not by RLlib: parity unpinned (DESIGN.md §3
 One PPO iteration on one GPU (all launches on torch's current stream, no host sync inside):
   rollout   rlks_rollout: T x (policy forward -> sample -> env step), bootstrap V(s_T)
   advantages rlks_gae -> rlks_adv_stats -> [all-reduce] -> rlks_adv_finalize
+  metrics   only with config.rollout_metrics: rlks_rollout_metrics (result["custom_metrics"])
   update    num_sgd_iter x minibatches x (rlks_ppo_gather -> rlks_ppo_grad -> [all-reduce] ->
             rlks_adam_step); then rlks_kl_update from the mean KL over all SGD steps.  Single rank:
             rlks_ppo_sgd_step_next per minibatch (gradient + Adam, and the next minibatch's gather
@@ -103,6 +104,9 @@ class PPOConfig:
         # rlks.metrics.JsonLinesReporter: append every train() result to this file as one JSON line
         # (also: $RLKS_METRICS_JSONL)
         self.metrics_json_lines = None
+        # per-iteration rollout metrics reduced on the device (rlks_rollout_metrics):
+        # train() reports them as result["custom_metrics"].  Off: nothing is allocated or launched
+        self.rollout_metrics = False
         # save() with no directory: this run's logdir under rlks.checkpoints.results_root()
         # (~/ray_results/PPO_<env>_<time>, RLlib's Algorithm.logdir)
         self.logdir = None
@@ -188,9 +192,11 @@ class PPOConfig:
             self.evaluation_baselines = validate_baselines(evaluation_baselines)
         return self
 
-    def reporting(self, metrics_num_episodes_for_smoothing=None, json_lines=None, **kw):
+    def reporting(self, metrics_num_episodes_for_smoothing=None, json_lines=None, rollout_metrics=None, **kw):
         if json_lines is not None:
             self.metrics_json_lines = str(json_lines)
+        if rollout_metrics is not None:
+            self.rollout_metrics = bool(rollout_metrics)
         if metrics_num_episodes_for_smoothing is not None:
             w = int(metrics_num_episodes_for_smoothing)
             # the window is filled from the device episode log, which keeps RLKS_EPLOG_CAP episodes
@@ -373,6 +379,21 @@ class PPO:
             self.coeffs = _lib.PpoCoeffs(cfg.clip_param, cfg.vf_clip_param, cfg.vf_loss_coeff, cfg.entropy_coeff)
             _lib.call("rlks_env_reset", self.env.handle, None, _lib.ptr(b["obs"][0]), self.stream)
             self.env.episode_log(clear=True)
+            # rollout metrics (opt-in): the record, the reduction's workspace and, on a node-level env,
+            # the env's pod counters, switched on once here and read as per-iteration deltas
+            self.rm_out = self.rm_ws = self.rm_counters = None
+            self.rollout_record = None  # the last iteration's record over all ranks (host, numpy)
+            if cfg.rollout_metrics:
+                size = _lib.lib().rlks_rollout_metrics_size(A, C_)
+                _lib.check(min(size, 0), "rlks_rollout_metrics_size")
+                rmb = C.c_int64()
+                _lib.call("rlks_rollout_metrics_workspace_bytes", T, N, A, C_, C.byref(rmb))
+                self.rm_out = torch.zeros(size, dtype=torch.float64, device=self.device)
+                self.rm_ws = torch.empty(rmb.value // 8, dtype=torch.float64, device=self.device)
+                if cfg.nodes is not None:
+                    self.rm_counters = torch.zeros(6, dtype=torch.int64, device=self.device)
+                    self._counters_seen = np.zeros(6, np.int64)
+                    _lib.call("rlks_env_counters", self.env.handle, 1, None, self.stream)
         # obs[0] holds the lanes' current observations only before the first rollout; afterwards
         # they are obs[T] of the previous rollout (moved to obs[0] when the next one starts, so the
         # update can still read obs[0..T-1])
@@ -549,6 +570,9 @@ class PPO:
         self._apply_schedules()
         self.rollout(explore=self.config.explore)
         self.advantages()
+        if self.rm_out is not None:
+            _lib.call("rlks_rollout_metrics", C.byref(self.bufs), self.D, self.A, self.A, _lib.ptr(self.rm_out),
+                      _lib.ptr(self.rm_ws), self.rm_ws.numel() * 8, self.stream)
         self.update()
         _lib.call("rlks_env_episode_stats", self.env.handle, _lib.ptr(self.ep_stats), 1, self.stream)
         self.iteration += 1
@@ -615,6 +639,34 @@ class PPO:
         rets, keys = np.concatenate(rets), np.concatenate(keys)
         return rets[np.argsort(keys, kind="stable")], total
 
+    def _rollout_metrics(self):
+        """result["custom_metrics"] of the iteration just run (rlks.rollout_metrics): the device record
+        and, on a node-level env, the pod counters' growth since the last call, over all ranks"""
+        from .rollout_metrics import combine, summarise
+
+        torch = self.torch
+        mine = [self.rm_out]
+        if self.rm_counters is not None:
+            _lib.call("rlks_env_counters", self.env.handle, -1, _lib.ptr(self.rm_counters), self.stream)
+            now = self.rm_counters.cpu().numpy()
+            delta = now - self._counters_seen  # integers; as doubles below they are exact (< 2^53)
+            self._counters_seen = now
+            mine.append(torch.from_numpy(delta.astype(np.float64)).to(self.device))
+        mine = torch.cat(mine)
+        if self.world == 1:
+            rows = mine.cpu().numpy()[None]
+        else:  # one zero-padded [world, k] matrix through the sum all-reduce, as _episode_returns
+            allv = torch.zeros(self.world, mine.numel(), dtype=torch.float64, device=self.device)
+            allv[self.rank] = mine
+            self._allreduce(allv)
+            rows = allv.cpu().numpy()
+        k = self.rm_out.numel()
+        self.rollout_record = combine(list(rows[:, :k]))
+        counters = None
+        if self.rm_counters is not None:
+            counters = np.rint(rows[:, k:]).astype(np.int64).sum(0)
+        return summarise(self.rollout_record, self.A, self.A, counters)
+
     def _reward_mean(self, ep_sum, n_ep):
         """RLlib episode_reward_mean: the mean over this iteration's episodes, topped up with the
         most recent earlier ones to metrics_num_episodes_for_smoothing (Algorithm.
@@ -680,6 +732,7 @@ class PPO:
             "cur_kl_coeff": kl_before,
             "cur_lr": self.cur_lr,
         }
+        custom = self._rollout_metrics() if self.rm_out is not None else None
         if self.grad_clip is not None:
             # RLlib's grad_gnorm: the norm before clipping, a mean over the SGD steps.  Every rank
             # wrote the same norm and self.stats was sum-all-reduced: divide by the world size
@@ -694,6 +747,8 @@ class PPO:
             "num_env_steps_sampled": self.timesteps_total,
             "info": {"learner": {"default_policy": {"learner_stats": learner}}},
         }
+        if custom is not None:
+            result["custom_metrics"] = custom
         # RLlib Algorithm.step(): evaluate when (iteration) % evaluation_interval == 0, after training
         iv = self.config.evaluation_interval
         if iv and self.iteration % int(iv) == 0:
