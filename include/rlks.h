@@ -454,6 +454,51 @@ int rlks_rollout_metrics_workspace_bytes(int T, int N, int A, int C, int64_t* by
 int rlks_rollout_metrics(const rlks_rollout_bufs* bufs, int D, int A, int C, double* out_dev,
                          void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* ============================================================== observation filter ======== */
+/* PPOConfig.rollouts(observation_filter="MeanStdFilter"): RLlib's (x - mean) / (std + 1e-8)
+ * per observation column with the unbiased running variance, no clipping.  RLlib is absent from the
+ * reference tree; the arithmetic below is the specification, restated in numpy by tests/obs_filter_ref.py.
+ * State: double[rlks_obs_filter_size(D)], the RLKS_OF_* layout of rlks_types.h; observations are row-major
+ * [rows][D].  1 <= D <= 512 (2 x 4 KB of LDS tables; the largest env here has D = 288); beyond that, for a
+ * null or misaligned pointer (floats 4-byte, doubles 8-byte aligned), rows < 0 or a workspace that is too
+ * small: RLKS_ERR_ARG and nothing is launched.  Every entry is asynchronous on `stream` and capturable.
+ *   init    count = 0, mean = 0, m2 = 0, inv = 1: the identity filter.
+ *   apply   y = (float)(((double)x - mean[d]) * inv[d]): one f64 subtract, one f64 multiply, one
+ *           conversion, never contracted.  y_dev == x_dev (in place) is allowed, any other overlap is not.
+ *           Reads the state, never writes it.  16-byte accesses when x_dev and y_dev are 16-byte aligned.
+ *   stats   record_dev = double[RLKS_OFR_SUMS + 2 D] = {rows, s1[D], s2[D]} over x_dev[rows][D], s1[d] =
+ *           sum (x - K[d]), s2[d] = sum (x - K[d])^2 in f64, K = the state's mean read on the device (the
+ *           shift keeps m2 free of the sum x^2 - n mean^2 cancellation).  Two launches; the grid and the
+ *           order of every addition depend on (rows, D) alone and there are no floating-point atomics: the
+ *           same input gives the same bits on every run.  The workspace (8-byte aligned) holds nothing
+ *           between calls.  rows = 0 gives a record of zeros.
+ *   merge   Chan's update with na = count, nb = record[0], n = na + nb, in f64, every operation rounded on
+ *           its own:  delta = s1 / nb;  mean' = mean + delta * (nb / n);
+ *           m2' = max(0, (m2 + (s2 - s1 * delta)) + (delta * delta) * ((na * nb) / n));
+ *           inv' = 1 / (sqrt(m2' / (n - 1)) + 1e-8) when n >= 2, else 1;  count' = n.
+ *           nb = 0 leaves the state unchanged.  The record is taken as handed over: several ranks sum their
+ *           records (all-reduce) first, K being the same on all of them.  One workgroup. */
+int rlks_obs_filter_size(int D); /* doubles in the state; negative RLKS_ERR_* for a bad D */
+int rlks_obs_filter_init(double* state_dev, int D, void* stream);
+int rlks_obs_filter_apply(const double* state_dev, const float* x_dev, float* y_dev, int64_t rows, int D,
+                          void* stream);
+int rlks_obs_filter_workspace_bytes(int64_t rows, int D, int64_t* bytes);
+int rlks_obs_filter_stats(const double* state_dev, const float* x_dev, int64_t rows, int D, double* record_dev,
+                          void* workspace_dev, int64_t workspace_bytes, void* stream);
+int rlks_obs_filter_merge(double* state_dev, const double* record_dev, int D, void* stream);
+
+/* rlks_rollout_ws with the filter between the env and the policy: the same dispatch and the same
+ * launches, except that the env's observation output of step t goes to raw_dev[t + 1] (raw_dev is
+ * float[T + 1][N][D]) and one rlks_obs_filter_apply launch per step writes bufs->obs[t + 1] =
+ * filter(raw[t + 1]) before the next forward reads it.  The caller provides raw[0]; the entry filters it
+ * into bufs->obs[0] first.  The state is read, never updated: the filter is frozen while a rollout runs.
+ * A split-fp16 table rollout takes the per-step kernels at every lane count (the persistent T-step
+ * kernel keeps its observations to itself).  workspace may be NULL for the fp32 kernels, as for
+ * rlks_rollout. */
+int rlks_rollout_filtered(rlks_env* env, const rlks_mlp_desc* desc, const float* params_dev,
+                          const rlks_rollout_bufs* bufs, int explore, void* workspace, int64_t ws_bytes,
+                          const double* state_dev, float* raw_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

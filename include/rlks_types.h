@@ -166,6 +166,25 @@ enum {
   RLKS_RM_FIXED = 10
 };
 
+/* Observation-filter state (rlks_obs_filter_*): double[RLKS_OF_VECS + RLKS_OF_NVEC * D] =
+ * the row count, then three vectors over the D observation columns; vector v of column d lies at
+ * [RLKS_OF_VECS + v * D + d].  A fresh state is count 0, mean 0, m2 0, inv 1: the identity. */
+enum {
+  RLKS_OF_COUNT = 0, /* observations merged so far (an integer held in a double) */
+  RLKS_OF_VECS = 1,  /* the first vector starts here */
+  RLKS_OF_MEAN = 0,  /* running mean */
+  RLKS_OF_M2 = 1,    /* sum of squared deviations from the mean */
+  RLKS_OF_INV = 2,   /* 1 / (sqrt(m2 / (count - 1)) + 1e-8) when count >= 2, else 1 */
+  RLKS_OF_NVEC = 3
+};
+/* Batch record of rlks_obs_filter_stats: double[RLKS_OFR_SUMS + 2 D] = rows, then s1[D] = sum (x - K[d])
+ * and s2[D] = sum (x - K[d])^2 with K = the state's mean when the record was taken.  Plain sums: the
+ * records of several ranks with equal states add. */
+enum {
+  RLKS_OFR_ROWS = 0,
+  RLKS_OFR_SUMS = 1
+};
+
 #ifdef __cplusplus
 }
 #endif

@@ -774,7 +774,7 @@ static int check_desc(const rlks_mlp_desc* d) {
 // obs[t + 1], f32 rewards[t], dones[t]); then the bootstrap V(obs[T]).  `w` = the split-fp16
 // weights (SF16) or nullptr (fp32 kernels).
 static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
-                        int explore, const SfWs* w, hipStream_t s) {
+                        int explore, const SfWs* w, hipStream_t s, const ObsTap* tap) {
   const int N = b->N, D = d->obs_dim, A = d->n_actions;
   const Layout L = make_layout(D, HID, A);
   SfFwdArgs r{};
@@ -805,12 +805,14 @@ static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* para
     }
     return RLKS_OK;
   };
+  if (int rc = tap_apply(tap, b, D, 0, s)) return rc;
   for (int t = 0; t < b->T; ++t) {
     const size_t tN = (size_t)t * N;
     if (int rc = forward(b->obs + tN * D, b->logits + tN * A, b->values + tN)) return rc;
     if (int rc = rlks_env_sample_step(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN,
-                                      b->obs + (tN + N) * D, b->rewards + tN, b->dones + tN, s))
+                                      tap_obs_out(tap, b, D, t + 1), b->rewards + tN, b->dones + tN, s))
       return rc;
+    if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
   }
   return forward(b->obs + (size_t)b->T * N * D, nullptr, b->values + (size_t)b->T * N);
 }
@@ -1617,8 +1619,11 @@ int rlks_kl_update(float* dyn, const double* kc, float target, void* stream) {
   return RLKS_OK;
 }
 
-int rlks_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
-                 int explore, void* stream) {
+// The rollout entries share their host loops; `tap` (obs_filter.h) is rlks_rollout_filtered's filter
+// between the env and the policy, nullptr for the unfiltered entries, which then issue exactly the
+// launches they always did.
+static int rollout_fp32(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
+                        int explore, const ObsTap* tap, void* stream) {
   if (int rc = check_desc(d)) return rc;
   RLKS_REQUIRE(!is_wide(d), RLKS_ERR_UNSUPPORTED, "rlks_rollout: this MLP / env needs rlks_rollout_ws");
   RLKS_REQUIRE(env && params && b && b->T > 0 && b->N > 0, RLKS_ERR_ARG, "rlks_rollout: bad argument");
@@ -1629,7 +1634,7 @@ int rlks_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, con
   hipStream_t s = (hipStream_t)stream;
   if (cfg.nodes_per_cluster > 0) {
     RLKS_REQUIRE(cfg.autoreset, RLKS_ERR_ARG, "rlks_rollout: node-level rollout needs autoreset lanes");
-    return node_rollout(env, d, params, b, explore, nullptr, s);
+    return node_rollout(env, d, params, b, explore, nullptr, s, tap);
   }
   const int N = b->N, D = d->obs_dim, A = d->n_actions;
   const Layout L = make_layout(D, d->hidden, A);
@@ -1638,15 +1643,17 @@ int rlks_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, con
   f.P = net_ptrs_host(params, L, 0);
   f.x_stride = D; f.M = N; f.D = D; f.A_pi = A;
   f.env = view(env); f.tab_cost = env->d_cost; f.tab_lat = env->d_lat; f.explore = explore;
+  if (int rc = tap_apply(tap, b, D, 0, s)) return rc;
   for (int t = 0; t < b->T; ++t) {
     f.x = b->obs + (size_t)t * N * D;
     f.out = b->logits + (size_t)t * N * A;
-    f.obs_next = b->obs + (size_t)(t + 1) * N * D;
+    f.obs_next = tap_obs_out(tap, b, D, t + 1);
     f.logp = b->logp + (size_t)t * N;
     f.actions = b->actions + (size_t)t * N;
     f.rewards = b->rewards + (size_t)t * N;
     f.dones = b->dones + (size_t)t * N;
     if (int rc = launch_fwd_head(f, 0, A, FWD_ROLLOUT, s)) return rc;
+    if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
   }
   // values of every visited observation (incl. the bootstrap obs[T]) in one batched pass
   FwdArgs v{};
@@ -1655,8 +1662,8 @@ int rlks_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, con
   return launch_fwd_head(v, 1, A, FWD_ONLY, s);
 }
 
-int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
-                    int explore, void* workspace, int64_t ws_bytes, void* stream) {
+static int rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
+                      int explore, void* workspace, int64_t ws_bytes, const ObsTap* tap, void* stream) {
   if (int rc = check_desc(d)) return rc;
   if (is_wide(d)) {
     RLKS_REQUIRE(env && params && b && b->T > 0 && b->N > 0 && workspace, RLKS_ERR_ARG, "rlks_rollout_ws: bad argument");
@@ -1666,9 +1673,9 @@ int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, 
                  RLKS_ERR_ARG, "rlks_rollout_ws: env / policy / buffer shapes disagree (autoreset lanes required)");
     const WideWs w = wide_ws_layout(d->obs_dim, d->hidden, d->n_actions, b->N, (char*)workspace);
     RLKS_REQUIRE(ws_bytes >= w.bytes, RLKS_ERR_ARG, "rlks_rollout_ws: workspace too small");
-    return wide_rollout(env, d, params, b, explore, w, (hipStream_t)stream);
+    return wide_rollout(env, d, params, b, explore, w, (hipStream_t)stream, tap);
   }
-  if (!is_sf(d)) return rlks_rollout(env, d, params, b, explore, stream);
+  if (!is_sf(d)) return rollout_fp32(env, d, params, b, explore, tap, stream);
   RLKS_REQUIRE(env && params && b && b->T > 0 && b->N > 0 && workspace, RLKS_ERR_ARG, "rlks_rollout_ws: bad argument");
   rlks_env_cfg cfg;
   rlks_env_config(env, &cfg);
@@ -1680,14 +1687,17 @@ int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, 
   hipStream_t s = (hipStream_t)stream;
   if (cfg.nodes_per_cluster > 0) {
     RLKS_REQUIRE(cfg.autoreset, RLKS_ERR_ARG, "rlks_rollout_ws: node-level rollout needs autoreset lanes");
-    return node_rollout(env, d, params, b, explore, &w, s);
+    return node_rollout(env, d, params, b, explore, &w, s, tap);
   }
   // by the whole job's lane count: W ranks of N lanes and one rank of W N lanes (num_lane_groups = W)
   // run the same forward kernel, so their logits, and hence their sampled actions, agree bit for bit
   const int64_t job_lanes = b->global_lanes > 0 ? b->global_lanes : N;
-  if (job_lanes > SF_ROLL_FUSED_MAX_LANES && cfg.autoreset) {
+  RLKS_REQUIRE(!tap || cfg.autoreset, RLKS_ERR_ARG, "rlks_rollout_filtered: autoreset lanes required");
+  if (tap || (job_lanes > SF_ROLL_FUSED_MAX_LANES && cfg.autoreset)) {
     // per step: the 16-row forward of both nets (k_sf_fwd16), then the fused sample + env step
-    // (k_sample_step, auto-reset lanes); V(obs[T]) by one more forward
+    // (k_sample_step, auto-reset lanes); V(obs[T]) by one more forward.  Filtered rollouts take this
+    // branch at every lane count: the persistent kernel below reads and writes one buffer inside a
+    // single launch, so no filter can stand between its env and its forward
     if (int rc = sf_prep(d, w, params, s, true)) return rc;
     const Layout L = make_layout(D, HID, A);
     SfFwdArgs f{};
@@ -1697,6 +1707,7 @@ int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, 
       f.n[net].b2 = P.b2; f.n[net].w3 = P.w3; f.n[net].b3 = P.b3;
     }
     f.M = N; f.D = D;
+    if (int rc = tap_apply(tap, b, D, 0, s)) return rc;
     for (int t = 0; t <= b->T; ++t) {
       const size_t tN = (size_t)t * N;
       f.x = b->obs + tN * D;
@@ -1705,8 +1716,9 @@ int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, 
       if (int rc = launch_sf_fwd16(f, A, s)) return rc;
       if (t == b->T) break;
       if (int rc = rlks_env_sample_step(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN,
-                                        b->obs + (tN + N) * D, b->rewards + tN, b->dones + tN, s))
+                                        tap_obs_out(tap, b, D, t + 1), b->rewards + tN, b->dones + tN, s))
         return rc;
+      if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
     }
     return RLKS_OK;
   }
@@ -1729,6 +1741,25 @@ int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, 
   a.rewards = b->rewards;
   a.dones = b->dones;
   return launch_sf_roll(a, FWD_ROLLOUT, s);
+}
+
+int rlks_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
+                 int explore, void* stream) {
+  return rollout_fp32(env, d, params, b, explore, nullptr, stream);
+}
+
+int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
+                    int explore, void* workspace, int64_t ws_bytes, void* stream) {
+  return rollout_ws(env, d, params, b, explore, workspace, ws_bytes, nullptr, stream);
+}
+
+int rlks_rollout_filtered(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b,
+                          int explore, void* workspace, int64_t ws_bytes, const double* state, float* raw,
+                          void* stream) {
+  RLKS_REQUIRE(state && raw && d && b && b->obs, RLKS_ERR_ARG, "rlks_rollout_filtered: null argument");
+  if (int n = rlks_obs_filter_size(d->obs_dim); n < 0) return n;
+  const ObsTap tap{state, raw};
+  return rollout_ws(env, d, params, b, explore, workspace, ws_bytes, &tap, stream);
 }
 
 }  // extern "C"

@@ -53,6 +53,8 @@ enum DcheckSite {
   DC_SGD_TILE = 7,     // F1 / F2 tile < M / 16
   DC_GEMM_K = 8,       // pre-split GEMM: a DMA piece's 8 halves within the plane's row (ld)
   DC_WIDE_COL = 9,     // wide dZ2 kernel: the thread's 8 columns within H
+  DC_FILTER_COL = 10,  // observation filter: the element's column < D
+  DC_FILTER_IDX = 11,  // observation filter: the float group / row within the input
 };
 #ifdef RLKS_DEBUG
 // every translation unit that includes this header gets its own counters and registers their

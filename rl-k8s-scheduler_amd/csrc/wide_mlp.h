@@ -2,6 +2,7 @@
 #pragma once
 
 #include "mlp_common.h"
+#include "obs_filter.h"
 
 namespace rlks {
 
@@ -34,6 +35,6 @@ int wide_grad(const rlks_mlp_desc* d, const rlks_ppo_coeffs* co, const float* pa
 int launch_sample(const EnvView& v, const float* logits, int A, int explore, int32_t* actions, float* logp,
                   hipStream_t s);
 int wide_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b, int explore,
-                 const WideWs& w, hipStream_t s);
+                 const WideWs& w, hipStream_t s, const ObsTap* tap = nullptr);
 
 }  // namespace rlks

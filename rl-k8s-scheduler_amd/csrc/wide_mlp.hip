@@ -716,28 +716,33 @@ int launch_sample(const EnvView& v, const float* logits, int A, int explore, int
 }
 
 int wide_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, const rlks_rollout_bufs* b, int explore,
-                 const WideWs& w, hipStream_t s) {
+                 const WideWs& w, hipStream_t s, const ObsTap* tap) {
   const int N = b->N, D = d->obs_dim, A = d->n_actions;
   RLKS_REQUIRE(w.M >= N, RLKS_ERR_ARG, "rlks_rollout_ws: workspace rows < envs");
   const EnvView v = view(env);
+  // with a tap (rlks_rollout_filtered): the env writes raw[t + 1], one apply launch filters it into obs[t + 1]
+  if (int rc = tap_apply(tap, b, D, 0, s)) return rc;
   for (int t = 0; t < b->T; ++t) {
     const float* obs = b->obs + (size_t)t * N * D;
+    float* obs_out = tap_obs_out(tap, b, D, t + 1);
     if (int rc = wide_forward(d, params, obs, D, N, w, b->logits + (size_t)t * N * A, b->values + (size_t)t * N, s))
       return rc;
     if (v.nodes > 0) {  // node-level env: Categorical sample + step in one launch (the sampling node step)
       if (int rc = rlks_env_sample_step(env, b->logits + (size_t)t * N * A, explore, b->actions + (size_t)t * N,
-                                        b->logp + (size_t)t * N, b->obs + (size_t)(t + 1) * N * D,
+                                        b->logp + (size_t)t * N, obs_out,
                                         b->rewards + (size_t)t * N, b->dones + (size_t)t * N, s))
         return rc;
+      if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
       continue;
     }
     if (int rc = launch_sample(v, b->logits + (size_t)t * N * A, A, explore, b->actions + (size_t)t * N,
                                b->logp + (size_t)t * N, s))
       return rc;
-    if (int rc = rlks_env_step(env, b->actions + (size_t)t * N, b->obs + (size_t)(t + 1) * N * D, nullptr,
+    if (int rc = rlks_env_step(env, b->actions + (size_t)t * N, obs_out, nullptr,
                                b->rewards + (size_t)t * N, b->dones + (size_t)t * N, nullptr, nullptr, nullptr, nullptr,
                                s))
       return rc;
+    if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
   }
   return wide_forward(d, params, b->obs + (size_t)b->T * N * D, D, N, w, nullptr, b->values + (size_t)b->T * N, s);
 }

@@ -31,6 +31,9 @@ RLKS_EPLOG_CAP = 128
  RLKS_RM_VTARG_SUM, RLKS_RM_VTARG_SQ, RLKS_RM_RESID_SUM, RLKS_RM_RESID_SQ, RLKS_RM_FIXED) = range(11)
 (RLKS_RULE_ROUND_ROBIN, RLKS_RULE_CHEAPEST, RLKS_RULE_MYOPIC, RLKS_RULE_LEAST_LOADED, RLKS_RULE_MYOPIC_WITH_ROOM,
  RLKS_RULE_RANDOM) = range(6)
+# observation-filter state / record layout (include/rlks_types.h RLKS_OF_*, RLKS_OFR_*)
+RLKS_OF_COUNT, RLKS_OF_VECS, RLKS_OF_MEAN, RLKS_OF_M2, RLKS_OF_INV, RLKS_OF_NVEC = 0, 1, 0, 1, 2, 3
+RLKS_OFR_ROWS, RLKS_OFR_SUMS = 0, 1
 # rule names of the Python surface (VecK8sMultiCloudEnv.rule_actions, rlks.evaluation) -> RLKS_RULE_*
 RULES = {"round_robin": RLKS_RULE_ROUND_ROBIN, "cheapest": RLKS_RULE_CHEAPEST, "myopic": RLKS_RULE_MYOPIC,
          "least_loaded": RLKS_RULE_LEAST_LOADED, "myopic_with_room": RLKS_RULE_MYOPIC_WITH_ROOM,
@@ -161,6 +164,13 @@ SIGNATURES = {
     "rlks_rollout_metrics_size": [_I, _I],
     "rlks_rollout_metrics_workspace_bytes": [_I, _I, _I, _I, C.POINTER(_I64)],
     "rlks_rollout_metrics": [C.POINTER(RolloutBufs), _I, _I, _I, _P, _P, _I64, _P],
+    "rlks_obs_filter_size": [_I],
+    "rlks_obs_filter_init": [_P, _I, _P],
+    "rlks_obs_filter_apply": [_P, _P, _P, _I64, _I, _P],
+    "rlks_obs_filter_workspace_bytes": [_I64, _I, C.POINTER(_I64)],
+    "rlks_obs_filter_stats": [_P, _P, _I64, _I, _P, _P, _I64, _P],
+    "rlks_obs_filter_merge": [_P, _P, _I, _P],
+    "rlks_rollout_filtered": [_P, C.POINTER(MlpDesc), _P, C.POINTER(RolloutBufs), _I, _P, _I64, _P, _P, _P],
 }
 _RESTYPES = {"rlks_last_error": C.c_char_p, "rlks_version": C.c_char_p}
 

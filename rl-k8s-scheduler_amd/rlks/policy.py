@@ -63,6 +63,11 @@ class PolicyParams:
         self.shapes = tensor_shapes(self.D, self.H, self.A)
         self.device = device
         self.flat = torch.zeros(self.padded, dtype=torch.float32, device=device)
+        # optional rlks.obs_filter.ObsFilter (PPO sets its own with observation_filter="MeanStdFilter"):
+        # forward() then takes raw observations and filters them into a scratch tensor first, which
+        # covers every evaluation and serving path; the state is read, never updated (RLlib's update=False)
+        self.obs_filter = None
+        self._fobs = None
         self.init(seed)
 
     def view(self, i):
@@ -121,6 +126,10 @@ class PolicyParams:
         if values is None:
             values = torch.empty(n, dtype=torch.float32, device=obs.device)
         obs = obs.contiguous()
+        if self.obs_filter is not None:
+            if self._fobs is None or self._fobs.numel() < obs.numel() or self._fobs.device != obs.device:
+                self._fobs = torch.empty(obs.numel(), dtype=torch.float32, device=obs.device)
+            obs = self.obs_filter.apply(obs, self._fobs[: obs.numel()].view(obs.shape))
         stream = torch.cuda.current_stream(obs.device).cuda_stream
         if self.wide():  # generic-width path: needs a workspace for the activations
             wsb = C.c_int64()

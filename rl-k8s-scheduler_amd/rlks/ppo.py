@@ -15,6 +15,9 @@ the torch-CPU oracle under oracle/, not by RLlib: parity unpinned (DESIGN.md §3
 One PPO iteration on one GPU (all launches on torch's current stream, no host sync inside):
   rollout   rlks_rollout: T x (policy forward -> sample -> env step), bootstrap V(s_T)
   advantages rlks_gae -> rlks_adv_stats -> [all-reduce] -> rlks_adv_finalize
+            with config.observation_filter = "MeanStdFilter": rlks_rollout_filtered (one
+            rlks_obs_filter_apply launch per step), then rlks_obs_filter_stats -> [all-reduce] ->
+            rlks_obs_filter_merge
   metrics   only with config.rollout_metrics: rlks_rollout_metrics (result["custom_metrics"])
   update    num_sgd_iter x minibatches x (rlks_ppo_gather -> rlks_ppo_grad -> [all-reduce] ->
             rlks_adam_step); then rlks_kl_update from the mean KL over all SGD steps.  Single rank:
@@ -40,6 +43,7 @@ import numpy as np
 from . import _lib
 from . import distributed as ddp
 from .env import DeviceEnv, make_cfg
+from .obs_filter import ObsFilter, validate_observation_filter
 from .policy import PolicyParams
 from .schedules import schedule_value, validate_grad_clip, validate_schedule
 from .tables import load_table
@@ -107,6 +111,13 @@ class PPOConfig:
         # per-iteration rollout metrics reduced on the device (rlks_rollout_metrics):
         # train() reports them as result["custom_metrics"].  Off: nothing is allocated or launched
         self.rollout_metrics = False
+        # RLlib's observation_filter: "NoFilter" or "MeanStdFilter" (rlks.obs_filter): the
+        # running per-column (x - mean) / (std + 1e-8) on the device, frozen during a rollout and updated
+        # from all of its raw observations afterwards (RLlib updates per observation: the first iteration
+        # here runs the identity).  On: the raw observations are kept beside the filtered ones, (T + 1) x
+        # lanes x obs_dim x 4 bytes more per rank (about 0.4 GB at c4, 0.8 GB at c3, 1.6 GB at c5), and a
+        # split-fp16 table rollout runs its per-step kernels.  Off: nothing is allocated or launched
+        self.observation_filter = "NoFilter"
         # save() with no directory: this run's logdir under rlks.checkpoints.results_root()
         # (~/ray_results/PPO_<env>_<time>, RLlib's Algorithm.logdir)
         self.logdir = None
@@ -162,6 +173,8 @@ class PPOConfig:
             self.num_envs_per_worker = int(num_envs_per_worker)
         if rollout_fragment_length is not None:
             self.rollout_fragment_length = rollout_fragment_length
+        if "observation_filter" in kw:
+            validate_observation_filter(kw["observation_filter"])
         for k, v in kw.items():
             setattr(self, k, v)
         return self
@@ -280,6 +293,7 @@ class PPO:
             if getattr(cfg, name) is not None:
                 validate_schedule(getattr(cfg, name), name)
         validate_baselines(cfg.evaluation_baselines)
+        validate_observation_filter(cfg.observation_filter)  # again: from_dict does not go through rollouts()
         self.torch = torch
         self.rank, self.world = ddp.rank_world()
         self.multi = self.world > 1 or ddp.forced()  # the multi-rank SGD step (ddp.forced: one rank, RCCL)
@@ -377,7 +391,24 @@ class PPO:
             self.kl_sc = torch.zeros(2, dtype=torch.float64, device=self.device)
             self.ep_stats = torch.zeros(2, dtype=torch.float64, device=self.device)
             self.coeffs = _lib.PpoCoeffs(cfg.clip_param, cfg.vf_clip_param, cfg.vf_loss_coeff, cfg.entropy_coeff)
-            _lib.call("rlks_env_reset", self.env.handle, None, _lib.ptr(b["obs"][0]), self.stream)
+            # observation filter (opt-in): the state, the batch record and its workspace, and the raw
+            # observations [T + 1][N][D] the env writes; buf["obs"] then holds the filtered ones, which is
+            # all the SGD side reads.  The params carry the filter to every serving / evaluation forward
+            self.obs_filter = self.raw = self.raw_bufs = None
+            if cfg.observation_filter == "MeanStdFilter":
+                self.obs_filter = ObsFilter(D, self.device)
+                self.obs_filter.reserve((T + 1) * N)
+                self.raw = torch.zeros(T + 1, N, D, **f32)
+                self.params.obs_filter = self.obs_filter
+                # the rollout metrics read the utilisation columns: from the raw buffer
+                self.raw_bufs = _lib.RolloutBufs(self.raw.data_ptr(), b["logits"].data_ptr(), b["values"].data_ptr(),
+                                                 b["actions"].data_ptr(), b["logp"].data_ptr(),
+                                                 b["rewards"].data_ptr(), b["dones"].data_ptr(), b["adv"].data_ptr(),
+                                                 b["vtarg"].data_ptr(), T, N, N * self.world)
+            # the first rollout after construction also counts its row 0 (later ones carry it over)
+            self._filter_first = True
+            _lib.call("rlks_env_reset", self.env.handle, None,
+                      _lib.ptr((self.raw if self.raw is not None else b["obs"])[0]), self.stream)
             self.env.episode_log(clear=True)
             # rollout metrics (opt-in): the record, the reduction's workspace and, on a node-level env,
             # the env's pod counters, switched on once here and read as per-iteration deltas
@@ -439,6 +470,24 @@ class PPO:
     def rollout(self, explore=True):
         s = self.stream
         b = self.buf
+        if self.obs_filter is not None:
+            # the carry is raw: raw[0] <- raw[T]; the entry refilters it into obs[0] with the state the
+            # last merge left, then filters every step's observations with that same (frozen) state
+            f, raw = self.obs_filter, self.raw
+            if self._carry:
+                raw[0].copy_(raw[self.T])
+            self._carry = True
+            _lib.call("rlks_rollout_filtered", self.env.handle, C.byref(self.params.desc), _lib.ptr(self.params.flat),
+                      C.byref(self.bufs), int(explore), _lib.ptr(self.ws), self.ws.numel(), _lib.ptr(f.state),
+                      _lib.ptr(raw), s)
+            # every raw observation the env produced in this rollout, once: rows 1..T (+ row 0 the first
+            # time); the record is a plain sum, so ranks add theirs before the merge.  All on the stream
+            f.stats(raw if self._filter_first else raw[1:])
+            self._filter_first = False
+            if self.world > 1:
+                self._allreduce(f.record)
+            f.merge()
+            return
         if self._carry:
             b["obs"][0].copy_(b["obs"][self.T])
         self._carry = True
@@ -571,7 +620,7 @@ class PPO:
         self.rollout(explore=self.config.explore)
         self.advantages()
         if self.rm_out is not None:
-            _lib.call("rlks_rollout_metrics", C.byref(self.bufs), self.D, self.A, self.A, _lib.ptr(self.rm_out),
+            _lib.call("rlks_rollout_metrics", C.byref(self.raw_bufs if self.raw_bufs is not None else self.bufs), self.D, self.A, self.A, _lib.ptr(self.rm_out),
                       _lib.ptr(self.rm_ws), self.rm_ws.numel() * 8, self.stream)
         self.update()
         _lib.call("rlks_env_episode_stats", self.env.handle, _lib.ptr(self.ep_stats), 1, self.stream)
@@ -747,6 +796,8 @@ class PPO:
             "num_env_steps_sampled": self.timesteps_total,
             "info": {"learner": {"default_policy": {"learner_stats": learner}}},
         }
+        if self.obs_filter is not None:
+            result["info"]["learner"]["default_policy"]["obs_filter"] = self.obs_filter.summary()
         if custom is not None:
             result["custom_metrics"] = custom
         # RLlib Algorithm.step(): evaluate when (iteration) % evaluation_interval == 0, after training
@@ -800,8 +851,10 @@ class PPO:
         return int(self._sample(logits, explore).item())
 
     def current_obs(self):
-        """the lanes' current observations [N, D] (device)"""
-        return self.buf["obs"][self.T] if self._carry else self.buf["obs"][0]
+        """the lanes' current observations [N, D] (device): what the env returned, so raw ones under
+        an observation filter (compute_actions(current_obs()) filters them once)"""
+        o = self.raw if self.raw is not None else self.buf["obs"]
+        return o[self.T] if self._carry else o[0]
 
     def get_state(self):
         """everything a resumed run needs: weights, Adam moments and step, KL coefficient, counters,
@@ -822,6 +875,10 @@ class PPO:
             "sample_calls": self.sample_calls,
             "rank": self.rank, "world": self.world,
         }
+        if self.obs_filter is not None:
+            n, mean, m2, inv = self.obs_filter.numpy()
+            st["obs_filter"] = {"count": torch.tensor([n], dtype=torch.float64), "mean": torch.from_numpy(mean),
+                                "m2": torch.from_numpy(m2), "inv": torch.from_numpy(inv)}
         if self._checkpoint_env_state():
             st["env_state"] = self.env.save_state().cpu()
             st["current_obs"] = self.current_obs().detach().cpu().clone()
@@ -862,6 +919,8 @@ class PPO:
         tensors.update({k: st.pop(k) for k in ("lane_steps", "lane_episodes")})
         if "current_obs" in st:
             tensors["current_obs"] = st.pop("current_obs")
+        if "obs_filter" in st:
+            tensors.update({f"obs_filter/{k}": v for k, v in st.pop("obs_filter").items()})
         env_state = st.pop("env_state", None)
         if env_state is not None:
             env_state.numpy().tofile(path / f"env_state{sfx}.bin")
@@ -893,6 +952,10 @@ class PPO:
                              "(per-rank env lanes and files do not transfer between world sizes)")
         sfx = f".rank{self.rank}" if self.world > 1 else ""
         tensors = torch.load(path / f"state{sfx}.pt", weights_only=True)
+        of = {k[len("obs_filter/"):]: v for k, v in tensors.items() if k.startswith("obs_filter/")}
+        if bool(of) != (self.obs_filter is not None):
+            raise ValueError(f"checkpoint {path} was written with{'' if of else 'out'} an observation filter; this "
+                             f"algorithm has observation_filter={self.config.observation_filter!r}")
         sd = {k[len("weights/"):]: v for k, v in tensors.items() if k.startswith("weights/")}
         w = self.params.state_dict()
         for k, v in w.items():
@@ -927,10 +990,14 @@ class PPO:
         self._ep_history.clear()
         self._ep_history.extend(meta.get("episode_history", []))
         self.sample_calls = int(meta.get("sample_calls", 0))
+        if of:
+            self.obs_filter.load(float(of["count"][0]), of["mean"].numpy(), of["m2"].numpy(), of["inv"].numpy())
+            self._filter_first = float(of["count"][0]) == 0.0
         es = path / f"env_state{sfx}.bin"
         if es.exists() and "current_obs" in tensors:
             self.env.load_state(np.fromfile(es, dtype=np.uint8))
-            self.buf["obs"][0].copy_(tensors["current_obs"].to(self.device))
+            # (the raw carry row under an observation filter: the next rollout refilters it)
+            (self.raw if self.raw is not None else self.buf["obs"])[0].copy_(tensors["current_obs"].to(self.device))
             self._carry = False
             self.env.episode_log(clear=True)
         else:
