@@ -142,6 +142,38 @@ int rlks_env_rule_actions(rlks_env* env, int rule, const float* obs_dev, int32_t
 int rlks_sample_categorical(const float* logits_dev, int n, int A, const uint32_t* ids_dev, unsigned long long seed,
                             int explore, int32_t* actions_dev, float* logp_dev, void* stream);
 
+/* ---- invalid-action masking (room(), mask() and the sentinel: rlks_types.h).  Every entry
+ * is asynchronous on `stream`, reads nothing on the host and is capturable.  n_clouds (or A) > 64:
+ * RLKS_ERR_UNSUPPORTED; a NULL required pointer: RLKS_ERR_ARG.
+ *
+ * rlks_env_action_mask: mask_dev[lane] = mask(lane) for every lane, table and node-level envs alike. */
+int rlks_env_action_mask(rlks_env* env, uint64_t* mask_dev, void* stream);
+/* One launch: computes the lane's mask, overwrites logits_dev[lane][c] (in/out, [n_envs][n_clouds]) of the
+ * clusters without room with RLKS_MASKED_LOGIT, then draws the action from the masked row with
+ * rlks_env_sample_step's arithmetic and Philox counter {env_offset + lane, episode, step,
+ * RLKS_PURPOSE_ACTION << 16} under the env's key (explore != 0) or takes the argmax, lowest index of the
+ * maximum (explore == 0); logp_dev = log pi(action) of the masked distribution; mask_out_dev (may be NULL)
+ * gets the mask.  The env is not stepped: follow with rlks_env_step(status = NULL).  One difference from the
+ * unmasked draw: when no cumulative entry exceeds u (f32(u53) rounds to 1.0, about 2^-25 of the draws) the
+ * action is the highest-index unmasked cluster, not n_clouds - 1.  When every cluster has room, logits,
+ * actions and logp are bit for bit rlks_env_sample_step's. */
+int rlks_env_masked_sample(rlks_env* env, float* logits_dev, int explore, int32_t* actions_dev, float* logp_dev,
+                           uint64_t* mask_out_dev, void* stream);
+/* The same draw under the caller's masks mask_dev[n] (bit a set = action a allowed) with
+ * rlks_sample_categorical's counter convention; logits_dev[n][A] is masked in place.  A row whose mask has
+ * no bit among the low A is treated as unmasked (the masks live on the device: rejecting such a row would
+ * cost a host read). */
+int rlks_sample_categorical_masked(float* logits_dev, const uint64_t* mask_dev, int n, int A, const uint32_t* ids_dev,
+                                   unsigned long long seed, int explore, int32_t* actions_dev, float* logp_dev,
+                                   void* stream);
+/* on != 0: the rollouts of a node-level env (rlks_rollout, rlks_rollout_ws, rlks_rollout_filtered) run, per
+ * step, the forward, rlks_env_masked_sample on bufs->logits[t] in place and rlks_env_step with trusted
+ * actions instead of the forward and rlks_env_sample_step: the same number of launches; bufs->logits then
+ * holds the masked rows, which the gather and pack kernels carry into the minibatch records unchanged and
+ * the loss heads recognise (rlks_ppo_grad below).  The flag is read when a rollout is enqueued.  A table
+ * env: RLKS_ERR_UNSUPPORTED. */
+int rlks_env_set_action_masking(rlks_env* env, int on);
+
 /* Sum of completed-episode returns and their count over all lanes (double[2]); clear != 0
  * zeroes the accumulators (PPO result "episode_reward_mean", train_ppo.py:29-30). */
 int rlks_env_episode_stats(rlks_env* env, double* out_dev, int clear, void* stream);
@@ -283,7 +315,10 @@ int rlks_ppo_gather_packed(const rlks_mlp_desc* desc, const float* packed_dev, i
 /* Gradient of the RLlib PPO loss (mean over `rows`*world rows via dyn[INV_COUNT]) w.r.t. the
  * flat parameters -> grad_dev (padded_count floats).  stats_dev (double[RLKS_STAT_SIZE]) gets
  * the sums for reporting and the KL update.  workspace from rlks_ppo_workspace_bytes (the gradient's
- * scratch for `rows` rows, then the gradient-clipping entry points' norm scratch). */
+ * scratch for `rows` rows, then the gradient-clipping entry points' norm scratch).
+ * Masked actions (rlks_env_masked_sample): where a record's old logit is <= RLKS_MASKED_LOGIT_MAX, the
+ * policy heads use that old logit in place of the network's output for the action, so its probability,
+ * KL, entropy and gradient terms are exact zeros.  A record without such an entry is computed as ever. */
 int rlks_ppo_workspace_bytes(const rlks_mlp_desc* desc, int rows, int64_t* bytes);
 /* Diagnostics (tools/f1b_isolate.py): the split-fp16 step's dZ2 hand-off inside `workspace` for `rows`
  * minibatch rows: out[net] = dZ2 planes ([rows / 16 tiles][8][hi, lo][64][8] fp16, sgd_sf16.hip F1a),

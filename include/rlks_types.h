@@ -48,6 +48,20 @@ enum {
   RLKS_RULE_RANDOM = 5            /* uniform: rlks_sample_categorical's draw from all-zero logits */
 };
 
+/* Invalid-action masking on node-level envs (rlks_env_action_mask, rlks_env_masked_sample).
+ *   room(lane, c) = used_cpu[c][lane] / pod_cpu_m <
+ *                   nodes_per_cluster * min(node_cpu[c] / pod_cpu_m, node_mem[c] / pod_mem_mi),
+ *                   every term an integer: the RLKS_RULE_MYOPIC_WITH_ROOM predicate.
+ *   mask(lane)    = uint64_t, bit c set when room(lane, c); when no cluster has room, all n_clouds low bits
+ *                   (nothing to choose between: the rule's fallback).  A table env has room everywhere.
+ * The logit of a cluster without room is overwritten with RLKS_MASKED_LOGIT, and a logit counts as masked
+ * when it is <= RLKS_MASKED_LOGIT_MAX.  The sentinel is finite on purpose: with -inf the KL and entropy
+ * terms of the PPO loss become 0 * inf = NaN; with -1e30f a masked action gets expf(...) == 0 and its KL,
+ * entropy and gradient terms come out as exact zeros through the loss heads' existing arithmetic.  The
+ * logits of clusters with room are expected above RLKS_MASKED_LOGIT_MAX (any finite policy output is). */
+#define RLKS_MASKED_LOGIT (-1e30f)
+#define RLKS_MASKED_LOGIT_MAX (-1e29f)
+
 typedef struct rlks_env_cfg {
   int32_t n_envs;        /* lanes */
   int32_t n_rows;        /* T: table rows (reference: 100, normalized_rl_data.csv) */

@@ -45,6 +45,7 @@ struct rlks_env {
   long long* d_eplog_key;
   unsigned* d_eplog_n;
   double* d_epstat;  // [ceil(n_envs / EPS_LANES)][2] partial (sum, count) of rlks_env_episode_stats
+  int action_masking;  // rlks_env_set_action_masking: the rollouts' host loops read it (action_mask.hip)
 };
 
 namespace rlks {

@@ -809,9 +809,18 @@ static int node_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* para
   for (int t = 0; t < b->T; ++t) {
     const size_t tN = (size_t)t * N;
     if (int rc = forward(b->obs + tN * D, b->logits + tN * A, b->values + tN)) return rc;
-    if (int rc = rlks_env_sample_step(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN,
-                                      tap_obs_out(tap, b, D, t + 1), b->rewards + tN, b->dones + tN, s))
+    if (env->action_masking) {
+      // rlks_env_set_action_masking: the masked draw on logits[t] in place, then the trusted-actions node
+      // step: two launches for the sampling node step's one
+      if (int rc = rlks_env_masked_sample(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN, nullptr, s))
+        return rc;
+      if (int rc = rlks_env_step(env, b->actions + tN, tap_obs_out(tap, b, D, t + 1), nullptr, b->rewards + tN,
+                                 b->dones + tN, nullptr, nullptr, nullptr, nullptr, s))
+        return rc;
+    } else if (int rc = rlks_env_sample_step(env, b->logits + tN * A, explore, b->actions + tN, b->logp + tN,
+                                             tap_obs_out(tap, b, D, t + 1), b->rewards + tN, b->dones + tN, s)) {
       return rc;
+    }
     if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
   }
   return forward(b->obs + (size_t)b->T * N * D, nullptr, b->values + (size_t)b->T * N);

@@ -347,18 +347,23 @@ __device__ __forceinline__ void sf_loss_t(const SfArgs& g, const LossDyn& dy, co
     const float adv = (r.adv - dy.adv_mean) * dy.adv_invstd;
     const float logp_old = r.lpo;
     const int act = (int)r.act;
-    float mx = out[0], mo = lo[0];
+    // a masked action (old logit <= RLKS_MASKED_LOGIT_MAX, rlks_env_masked_sample) keeps its old logit: its
+    // probability, KL, entropy and gradient terms are then exact zeros
+    float lg[A_];
 #pragma unroll
-    for (int a = 1; a < A_; ++a) { mx = fmaxf(mx, out[a]); mo = fmaxf(mo, lo[a]); }
+    for (int a = 0; a < A_; ++a) lg[a] = lo[a] <= RLKS_MASKED_LOGIT_MAX ? lo[a] : out[a];
+    float mx = lg[0], mo = lo[0];
+#pragma unroll
+    for (int a = 1; a < A_; ++a) { mx = fmaxf(mx, lg[a]); mo = fmaxf(mo, lo[a]); }
     float se = 0.f, so = 0.f;
 #pragma unroll
-    for (int a = 0; a < A_; ++a) { se += expf(out[a] - mx); so += expf(lo[a] - mo); }
+    for (int a = 0; a < A_; ++a) { se += expf(lg[a] - mx); so += expf(lo[a] - mo); }
     const float lse = mx + logf(se), lso = mo + logf(so);
     float p[A_], lp[A_], po[A_];
     float kl = 0.f, ent = 0.f, lpa = 0.f;
 #pragma unroll
     for (int a = 0; a < A_; ++a) {
-      lp[a] = out[a] - lse;
+      lp[a] = lg[a] - lse;
       p[a] = expf(lp[a]);
       const float lpo = lo[a] - lso;
       po[a] = expf(lpo);

@@ -164,7 +164,11 @@ __global__ __launch_bounds__(64 * LOSS_PI_WAVES) void k_wide_loss_pi(const float
     const int m = blockIdx.x * LOSS_ROWS + w * RPW + i;
     if (m >= M) break;
     const float* rec = x + (size_t)m * stride;
-    const double lg = on ? (double)out[(size_t)m * A + l] : -INFINITY, lo = on ? (double)rec[D + l] : -INFINITY;
+    // a masked action (old logit <= RLKS_MASKED_LOGIT_MAX, rlks_env_masked_sample) keeps its old logit: its
+    // probability, KL, entropy and gradient terms are then exact zeros
+    const float lo_f = on ? rec[D + l] : 0.f;
+    const double lo = on ? (double)lo_f : -INFINITY;
+    const double lg = on ? (lo_f <= RLKS_MASKED_LOGIT_MAX ? lo : (double)out[(size_t)m * A + l]) : -INFINITY;
     const double adv = ((double)rec[D + A] - adv_mean) * adv_invstd;
     const double logp_old = rec[D + A + 2];
     const int act = (int)rec[D + A + 3];
@@ -727,6 +731,18 @@ int wide_rollout(rlks_env* env, const rlks_mlp_desc* d, const float* params, con
     float* obs_out = tap_obs_out(tap, b, D, t + 1);
     if (int rc = wide_forward(d, params, obs, D, N, w, b->logits + (size_t)t * N * A, b->values + (size_t)t * N, s))
       return rc;
+    if (v.nodes > 0 && env->action_masking) {
+      // rlks_env_set_action_masking: the masked draw on logits[t] in place, then the trusted-actions node
+      // step
+      if (int rc = rlks_env_masked_sample(env, b->logits + (size_t)t * N * A, explore, b->actions + (size_t)t * N,
+                                          b->logp + (size_t)t * N, nullptr, s))
+        return rc;
+      if (int rc = rlks_env_step(env, b->actions + (size_t)t * N, obs_out, nullptr, b->rewards + (size_t)t * N,
+                                 b->dones + (size_t)t * N, nullptr, nullptr, nullptr, nullptr, s))
+        return rc;
+      if (int rc = tap_apply(tap, b, D, t + 1, s)) return rc;
+      continue;
+    }
     if (v.nodes > 0) {  // node-level env: Categorical sample + step in one launch (the sampling node step)
       if (int rc = rlks_env_sample_step(env, b->logits + (size_t)t * N * A, explore, b->actions + (size_t)t * N,
                                         b->logp + (size_t)t * N, obs_out,

@@ -34,6 +34,9 @@ RLKS_EPLOG_CAP = 128
 # observation-filter state / record layout (include/rlks_types.h RLKS_OF_*, RLKS_OFR_*)
 RLKS_OF_COUNT, RLKS_OF_VECS, RLKS_OF_MEAN, RLKS_OF_M2, RLKS_OF_INV, RLKS_OF_NVEC = 0, 1, 0, 1, 2, 3
 RLKS_OFR_ROWS, RLKS_OFR_SUMS = 0, 1
+# invalid-action masking (include/rlks_types.h): the sentinel a masked logit is overwritten with, and the
+# threshold at or below which a logit counts as masked
+RLKS_MASKED_LOGIT, RLKS_MASKED_LOGIT_MAX = -1e30, -1e29
 # rule names of the Python surface (VecK8sMultiCloudEnv.rule_actions, rlks.evaluation) -> RLKS_RULE_*
 RULES = {"round_robin": RLKS_RULE_ROUND_ROBIN, "cheapest": RLKS_RULE_CHEAPEST, "myopic": RLKS_RULE_MYOPIC,
          "least_loaded": RLKS_RULE_LEAST_LOADED, "myopic_with_room": RLKS_RULE_MYOPIC_WITH_ROOM,
@@ -113,6 +116,10 @@ SIGNATURES = {
     "rlks_env_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rlks_env_sample_step": [_P, _P, _I, _P, _P, _P, _P, _P, _P],
     "rlks_env_rule_actions": [_P, _I, _P, _P, _P],
+    "rlks_env_action_mask": [_P, _P, _P],
+    "rlks_env_masked_sample": [_P, _P, _I, _P, _P, _P, _P],
+    "rlks_sample_categorical_masked": [_P, _P, C.c_int, C.c_int, _P, C.c_ulonglong, C.c_int, _P, _P, _P],
+    "rlks_env_set_action_masking": [_P, _I],
     "rlks_env_episode_stats": [_P, _P, _I, _P],
     "rlks_env_lane_state": [_P, _P, _P, _P],
     "rlks_env_episode_log": [_P, _P, _P, _P, _I, _P],

@@ -484,6 +484,34 @@ class VecK8sMultiCloudEnv:
                   self.dev.stream)
         return self._s_actions, self._s_logp, self.obs, self._s_reward, self._s_done
 
+    def action_mask(self):
+        """bool [N, C] on the device: True where the cluster can take one more pod (rlks_env_action_mask,
+        DESIGN.md §22): the "myopic_with_room" predicate on the clusters' used millicores; a row without
+        room anywhere is all True (nothing to choose between), as is every row of a table env.  A new
+        tensor per call.  More than 64 clusters: RlksError."""
+        torch = _torch()
+        bits = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
+        _lib.call("rlks_env_action_mask", self.handle, _lib.ptr(bits), self.dev.stream)
+        return ((bits[:, None] >> torch.arange(self.n_clouds, device=self.device)[None, :]) & 1).to(torch.bool)
+
+    def masked_sample(self, logits, explore=True):
+        """Categorical sample (explore) or argmax of `logits` [N, C] under the env's action mask, one kernel
+        launch (rlks_env_masked_sample); the env is not stepped.  `logits` is masked in place when it is a
+        contiguous float32 tensor on the env's device (else a masked copy is made and dropped): clusters
+        without room get _lib.RLKS_MASKED_LOGIT.  -> (actions int32 [N], logp f32 [N]) of the masked
+        distribution, device tensors owned by the env.  Lane i draws from the Philox counter sample_step()
+        uses: do not mix the two on one step."""
+        torch = _torch()
+        lg = torch.as_tensor(logits, device=self.device).to(torch.float32).contiguous()
+        if tuple(lg.shape) != (self.num_envs, self.n_clouds):
+            raise ValueError(f"masked_sample: logits must be [{self.num_envs}, {self.n_clouds}], got {list(lg.shape)}")
+        if not hasattr(self, "_m_actions"):
+            self._m_actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            self._m_logp = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)
+        _lib.call("rlks_env_masked_sample", self.handle, _lib.ptr(lg), int(bool(explore)), _lib.ptr(self._m_actions),
+                  _lib.ptr(self._m_logp), None, self.dev.stream)
+        return self._m_actions, self._m_logp
+
     def rule_actions(self, rule, obs=None):
         """One baseline-scheduler decision per lane on the device (rlks_env_rule_actions, DESIGN.md
         §19) -> actions int32 [N], a device tensor owned by the env (overwritten by the next call).

@@ -93,6 +93,17 @@ def _params_of(policy):
     return getattr(policy, "params", policy)
 
 
+def _mask_on(policy, action_mask, nodes):
+    """whether an evaluation decides under the env's action mask: action_mask None = the
+    setting of the PPO algorithm passed as `policy` (off for bare parameters and rules)"""
+    on = getattr(policy, "action_mask", None) is not None if action_mask is None else bool(action_mask)
+    if on and isinstance(policy, str):
+        raise ValueError("action_mask applies to a policy, not to a rule")
+    if on and nodes is None:
+        raise ValueError("action_mask needs a node-level env: a table env has room everywhere")
+    return on
+
+
 def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=None,
              baseline_cost: float = BASELINE_COST) -> EvalResult:
     """final_evaluation.py:39-77 batched: `policy` is a PPO algorithm / PolicyParams (greedy argmax,
@@ -160,15 +171,20 @@ def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=N
         env.close()
 
 
-def evaluate_lanes(params, num_episodes: int, *, table=None, nodes=None, seed=0, device=None) -> np.ndarray:
+def evaluate_lanes(params, num_episodes: int, *, table=None, nodes=None, seed=0, device=None,
+                   action_mask=None) -> np.ndarray:
     """Greedy (explore=False) float64 returns of `num_episodes` episodes, one lane each, all lanes
     in one batched env: RLlib's evaluation workers (train_final.py:19 .evaluation(
     evaluation_interval=5, evaluation_duration=20), evaluation explore=False).  Table envs run the
     reference-exact evaluate() above; node-level envs (configs c3 / c5) run Philox lanes keyed by
-    `seed` (episode e = lane e)."""
+    `seed` (episode e = lane e).  action_mask (None = the setting of a PPO algorithm passed as `params`,
+    off otherwise): decide with VecK8sMultiCloudEnv.masked_sample(logits, explore=False), the argmax over
+    the clusters with room."""
     import torch
 
     table = table if table is not None else load_table()
+    mask = _mask_on(params, action_mask, nodes)
+    params = _params_of(params)
     if nodes is None:
         return evaluate(params, num_episodes, seed=seed, table=table, device=device).rewards
     E = int(num_episodes)
@@ -181,7 +197,8 @@ def evaluate_lanes(params, num_episodes: int, *, table=None, nodes=None, seed=0,
         values = torch.empty(E, dtype=torch.float32, device=env.device)
         for _ in range(table.n_rows - 1):
             params.forward(obs, logits, values)
-            obs, r, term, _, _ = env.step(torch.argmax(logits, dim=1).to(torch.int32))
+            a = env.masked_sample(logits, explore=False)[0] if mask else torch.argmax(logits, dim=1).to(torch.int32)
+            obs, r, term, _, _ = env.step(a)
             ret += r
         env.check_status()
         return ret.cpu().numpy()
@@ -208,14 +225,17 @@ class NodeEvalResult:
         return self.rejected / n if n else 0.0
 
 
-def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, device=None) -> NodeEvalResult:
+def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, device=None,
+                   action_mask=None) -> NodeEvalResult:
     """`num_episodes` episodes of a node-level env (rlks.env.NodeSpec `nodes`), one lane each, every lane
     stepped by the same launches: episode e runs on lane e of a Philox env keyed by `seed`, with
     autoreset=False, for max_steps steps.  `policy`: a PPO algorithm or PolicyParams (greedy argmax, as
     evaluate_lanes and RLlib's evaluation workers, explore=False) or a rule name of rlks._lib.RULES
     (decided on the device by rlks_env_rule_actions).  Returns are summed in float64 in step order,
     as evaluate_lanes sums them; the pod counts are rlks_env_counters'.  The loop stays on the device:
-    everything is read back once at the end.
+    everything is read back once at the end.  action_mask (None = the setting of a PPO algorithm passed
+    as `policy`, off otherwise): the policy decides with masked_sample(logits, explore=False), the argmax
+    over the clusters with room.
 
     The comparison of two policies is paired: arrivals are keyed by (lane, episode, step), not by what
     was decided, so two calls with the same `seed` and episode count see the same arrival counts at
@@ -229,6 +249,7 @@ def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, devi
         raise ValueError("evaluate_nodes needs a NodeSpec; table envs are evaluate()'s")
     table = table if table is not None else load_table()
     C_ = table.n_clouds
+    mask = _mask_on(policy, action_mask, nodes)
     if isinstance(policy, str):
         if policy not in _lib.RULES:
             raise ValueError(f"unknown baseline policy {policy!r}; one of {sorted(_lib.RULES)}")
@@ -255,7 +276,7 @@ def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, devi
         for t in range(T):
             if params is not None:
                 params.forward(obs, logits, values)
-                a = torch.argmax(logits, dim=1).to(torch.int32)
+                a = env.masked_sample(logits, explore=False)[0] if mask else torch.argmax(logits, dim=1).to(torch.int32)
             else:
                 a = env.rule_actions(policy)
             actions[t] = a

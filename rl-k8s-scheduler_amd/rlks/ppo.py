@@ -18,6 +18,9 @@ One PPO iteration on one GPU (all launches on torch's current stream, no host sy
             with config.observation_filter = "MeanStdFilter": rlks_rollout_filtered (one
             rlks_obs_filter_apply launch per step), then rlks_obs_filter_stats -> [all-reduce] ->
             rlks_obs_filter_merge
+            with config.action_mask = "room" on a node-level env: every step's draw is
+            rlks_env_masked_sample on the step's logits in place, then the trusted-actions rlks_env_step
+            (rlks_env_set_action_masking)
   metrics   only with config.rollout_metrics: rlks_rollout_metrics (result["custom_metrics"])
   update    num_sgd_iter x minibatches x (rlks_ppo_gather -> rlks_ppo_grad -> [all-reduce] ->
             rlks_adam_step); then rlks_kl_update from the mean KL over all SGD steps.  Single rank:
@@ -60,6 +63,20 @@ def validate_baselines(names):
     if bad:
         raise ValueError(f"unknown evaluation baseline(s) {bad}; one of {sorted(_lib.RULES)}")
     return names
+
+
+def validate_action_mask(value, nodes=None, n_clouds=None):
+    """PPOConfig.action_mask: None (off) or "room" (rlks_env_masked_sample), which needs a
+    node-level env (a table env has room everywhere) of at most 64 clusters (a 64-bit mask)"""
+    if value is None:
+        return None
+    if value != "room":
+        raise ValueError(f"action_mask must be None or 'room', got {value!r}")
+    if nodes is None:
+        raise ValueError("action_mask='room' needs a node-level env (PPOConfig.nodes): a table env has room everywhere")
+    if n_clouds is not None and n_clouds > 64:
+        raise ValueError(f"action_mask='room' supports at most 64 clusters (a 64-bit mask), got {n_clouds}")
+    return "room"
 
 
 class PPOConfig:
@@ -118,6 +135,11 @@ class PPOConfig:
         # lanes x obs_dim x 4 bytes more per rank (about 0.4 GB at c4, 0.8 GB at c3, 1.6 GB at c5), and a
         # split-fp16 table rollout runs its per-step kernels.  Off: nothing is allocated or launched
         self.observation_filter = "NoFilter"
+        # invalid-action masking on node-level envs: None or "room".  "room": every rollout
+        # step masks the logits of the clusters that cannot take one more pod (the "myopic_with_room"
+        # predicate) before the draw, the stored logits carry the mask into the loss, and evaluation and
+        # compute_actions decide under a mask too.  No state.  None: nothing is allocated or launched
+        self.action_mask = None
         # save() with no directory: this run's logdir under rlks.checkpoints.results_root()
         # (~/ray_results/PPO_<env>_<time>, RLlib's Algorithm.logdir)
         self.logdir = None
@@ -305,6 +327,7 @@ class PPO:
         C_ = table.n_clouds
         if cfg.nodes is not None and cfg.nodes.n_clouds != C_:
             raise ValueError(f"NodeSpec has {cfg.nodes.n_clouds} clusters, the table {C_}")
+        self.action_mask = validate_action_mask(cfg.action_mask, cfg.nodes, C_)
         self.D, self.A, self.H = 3 * C_, C_, cfg.hidden()
         self.N = cfg.lanes()
         self.T = max(1, math.ceil(cfg.train_batch_size / (self.N * self.world)))
@@ -338,6 +361,8 @@ class PPO:
             self.env = DeviceEnv(make_cfg(self.N, table, noise=cfg.noise, seed=seed, autoreset=True,
                                           env_offset=ddp.lane_range(self.N, self.rank)[0], nodes=cfg.nodes),
                                  table, self.device, cfg.nodes)
+            if self.action_mask is not None:  # read by the rollout entries when a rollout is enqueued
+                _lib.call("rlks_env_set_action_masking", self.env.handle, 1)
             self.params = PolicyParams(self.D, self.H, self.A, device=self.device, seed=seed)
             prec = cfg.sgd_precision
             if self.params.wide():
@@ -735,15 +760,18 @@ class PPO:
         self._ep_history.extend(rets)
         return float(np.mean(vals)) if vals else float("nan")
 
-    def evaluate(self, episodes=None):
+    def evaluate(self, episodes=None, action_mask=None):
         """greedy evaluation (RLlib evaluation workers, explore=False): `episodes` episodes, one
-        lane each (train_final.py:19 .evaluation(evaluation_interval=5, evaluation_duration=20))"""
+        lane each (train_final.py:19 .evaluation(evaluation_interval=5, evaluation_duration=20)).
+        action_mask: None = this algorithm's own setting, else "room" or False"""
         from .evaluation import evaluate as evaluate_table
         from .evaluation import evaluate_lanes, evaluate_nodes
 
         n = int(episodes or self.config.evaluation_duration)
         seed = (self.seed * 7919 + self.iteration) & 0xFFFFFFFF
-        rets = evaluate_lanes(self.params, n, table=self.table, nodes=self.config.nodes, seed=seed, device=self.device)
+        mask = (self.action_mask is not None) if action_mask is None else bool(action_mask)
+        rets = evaluate_lanes(self.params, n, table=self.table, nodes=self.config.nodes, seed=seed, device=self.device,
+                              action_mask=mask)
         out = {"episode_reward_mean": float(np.mean(rets)), "episode_reward_min": float(np.min(rets)),
                "episode_reward_max": float(np.max(rets)), "episodes_this_iter": n,
                "episode_len_mean": float(self.table.n_rows - 1)}
@@ -813,13 +841,29 @@ class PPO:
     # lane has this id, so these draws never repeat a rollout draw under the same key (config.seed)
     SAMPLER_ID = 0xFFFFFFFF
 
-    def _sample(self, logits, explore):
+    def _sample(self, logits, explore, action_mask=None):
         """TorchCategorical sample (explore) or argmax of logits [n, A] on the device sampler
         (rlks_sample_categorical): row i draws Philox({SAMPLER_ID, i, call counter, ACTION},
         key = config.seed), so a run's exploring actions follow from the seed and the number of
-        earlier calls (the counter is checkpointed)"""
+        earlier calls (the counter is checkpointed).  action_mask: bool [n, A], True = allowed
+        (rlks_sample_categorical_masked; a row without a True counts as all True); an algorithm
+        configured with action_mask="room" must be given one"""
         torch = self.torch
         n = logits.shape[0]
+        bits = None
+        if action_mask is not None:
+            if self.A > 64:
+                raise ValueError(f"action_mask supports at most 64 actions, got {self.A}")
+            m = torch.as_tensor(action_mask, device=self.device).to(torch.bool).reshape(-1, self.A)
+            if m.shape[0] != n:
+                raise ValueError(f"action_mask must be [{n}, {self.A}], got {list(m.shape)}")
+            # bit a of row i = m[i, a]; bit 63 through the sign bit of the int64
+            w = torch.ones(self.A, dtype=torch.int64, device=self.device) << torch.arange(self.A, device=self.device)
+            bits = (m.to(torch.int64) * w[None, :]).sum(1).contiguous()
+        elif self.action_mask is not None:
+            raise ValueError("this algorithm was trained with action_mask='room': pass action_mask (bool [n, A], "
+                             "e.g. VecK8sMultiCloudEnv.action_mask()); a masked policy acting unmasked would be a "
+                             "silent error")
         logits = logits.contiguous()
         act = torch.empty(n, dtype=torch.int32, device=self.device)
         ids = None
@@ -830,25 +874,35 @@ class PPO:
             idh[:, 2] = self.sample_calls & 0xFFFFFFFF
             ids = torch.from_numpy(idh.view(np.int32)).to(self.device)
             self.sample_calls += 1
+        if bits is not None:
+            _lib.call("rlks_sample_categorical_masked", _lib.ptr(logits), _lib.ptr(bits), n, logits.shape[1],
+                      _lib.ptr(ids) if ids is not None else None, self.seed & 0xFFFFFFFFFFFFFFFF, int(bool(explore)),
+                      _lib.ptr(act), None, self.stream)
+            return act
         _lib.call("rlks_sample_categorical", _lib.ptr(logits), n, logits.shape[1], _lib.ptr(ids) if ids is not None else None,
                   self.seed & 0xFFFFFFFFFFFFFFFF, int(bool(explore)), _lib.ptr(act), None, self.stream)
         return act
 
-    def compute_actions(self, obs, explore=None):
-        """batched actions for obs [n, D] (device or host); returns an int32 device tensor"""
+    def compute_actions(self, obs, explore=None, action_mask=None):
+        """batched actions for obs [n, D] (device or host); returns an int32 device tensor.
+        action_mask: bool [n, A], True = allowed; required when the algorithm has action_mask="room"
+        (ValueError otherwise)"""
         torch = self.torch
         explore = self.config.explore if explore is None else explore
         o = torch.as_tensor(obs, dtype=torch.float32, device=self.device).reshape(-1, self.D)
         logits, _ = self.params.forward(o)
-        return self._sample(logits, explore)
+        return self._sample(logits, explore, action_mask)
 
-    def compute_single_action(self, observation=None, state=None, *, explore=None, **kw):
+    def compute_single_action(self, observation=None, state=None, *, explore=None, action_mask=None, **kw):
         """RLlib Algorithm.compute_single_action (eval_ppo.py:27 explores by default,
-        final_evaluation.py:48 passes explore=False): one observation -> int action"""
+        final_evaluation.py:48 passes explore=False): one observation -> int action.
+        action_mask: bool [A], as compute_actions'"""
         explore = self.config.explore if explore is None else explore
         o = np.asarray(observation, dtype=np.float32).reshape(1, self.D)
         logits, _ = self.params.forward(self.torch.from_numpy(o).to(self.device))
-        return int(self._sample(logits, explore).item())
+        if action_mask is not None:
+            action_mask = np.asarray(action_mask, dtype=bool).reshape(1, self.A)
+        return int(self._sample(logits, explore, action_mask).item())
 
     def current_obs(self):
         """the lanes' current observations [N, D] (device): what the env returned, so raw ones under
