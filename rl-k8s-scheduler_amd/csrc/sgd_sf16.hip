@@ -418,7 +418,9 @@ __device__ unsigned long long g_fa_stamps[2][8192][8];
   g_fa_stamps[NET][tile][7] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |       \
                               ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32)
 // F1b (f1b_body: k_sf_bwd, or the second half of k_sf_f1) the same way: 0 entry, 1 prologue landed,
-// 2 dH1 loop done, 3 Z1 recompute + dZ1 done, 4 Xa^T fragment ready, 5 dW1 products + flush done
+// 2 dH1 loop done, 3 Z1 recompute + dZ1 done, 4 Xa^T fragment ready, 5 dW1 products + flush done; the
+// k-tile-major F1b (f1b_kt_body): 0 entry, 1 constants and Xa fragments ready, 2 step 0 done, 3 step 9 done,
+// 4 step 15 done (the loop), 5 the tail (epilogue of k-tile 15, sums of k-tiles 14 and 15) done
 __device__ unsigned long long g_fb_stamps[2][8192][8];
 #define FB_STAMP(i) \
   if (l == 0 && tile < 8192) g_fb_stamps[NET][tile][i] = __builtin_amdgcn_s_memtime()
@@ -486,6 +488,20 @@ __device__ __forceinline__ void hc_dma(const _Float16* hi, const _Float16* lo, i
     const int blk = (16 / W) * w + i, arr = blk >> 3, sig = (blk & 7) * 64 + l;
     const int r = sig >> 2, q = (sig & 3) ^ sw16(r);
     const _Float16* src = (arr ? lo : hi) + (r0 + r) * HID + col + 8 * q;
+    _Float16* dst = buf + arr * H16 + (blk & 7) * 512;
+    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+  }
+}
+// the same image from rows [16 kt, 16 kt + 16) x all 256 columns (the k-tile-major F1b, f1b_kt_body):
+// image row 16 s + c holds row 16 kt + c, columns [32 s, 32 s + 32), so hc_frag(buf, s, ...) is the
+// fragment of n-step s; only the source addresses differ from hc_dma
+template <int W>
+__device__ __forceinline__ void hc_dma_kt(const _Float16* hi, const _Float16* lo, int kt, _Float16* buf, int w, int l) {
+#pragma unroll
+  for (int i = 0; i < 16 / W; ++i) {
+    const int blk = (16 / W) * w + i, arr = blk >> 3, sig = (blk & 7) * 64 + l;
+    const int r = sig >> 2, q = (sig & 3) ^ sw16(r);
+    const _Float16* src = (arr ? lo : hi) + (16 * kt + (r & 15)) * HID + 32 * (r >> 4) + 8 * q;
     _Float16* dst = buf + arr * H16 + (blk & 7) * 512;
     __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
   }
@@ -665,11 +681,17 @@ constexpr int f1b_lds_bytes() {
 //   dW3[A-1] = -sum_{a < A-1} dW3[a]
 // which is the same loss and gradient with A - 1 head rows instead of A (at 2 actions: half of the
 // head, of dZ2's products and of the dW3 reduce-scatter, the epilogue's largest part).  AH: head rows.
-// the lane's dZ2 fragment of n-step 0 as F1a split it: k_sf_f1 hands it to F1b in registers, so that
-// F1b's prologue waits for no load (it reads the later n-steps back from the dz2s it shares with F2)
+// the lane's dZ2 fragments as F1a split them, by n-step: k_sf_f1 hands them to F1b in registers.  The
+// k-tile-major F1b (f1b_kt_body: KD = 16, three products) takes all eight and reads no dZ2 from memory;
+// f1b_body takes the first, so that its prologue waits for no load, and reads the later n-steps back
+// from the dz2s it shares with F2
 struct DzFrag {
   h8 h, l;
 };
+// whether k_sf_f1 runs the k-tile-major F1b after F1a (compile time: the kernel's default range, up to
+// 4 actions with three products; the fp16 throughput kernel and 8 actions keep f1b_body)
+template <int KD, int P, int XOFF>
+constexpr bool f1_ktile() { return KD == 16 && P == 3 && XOFF >= 0; }
 // XOFF >= 0 (k_sf_f1): the byte offset in the dynamic LDS of the waves' Xa images kept for F1b (xs_store)
 template <int A_, int NET, int KD, int W, int P, int XOFF = -1>
 __device__ __forceinline__ int2 f1a_body(const SfArgs& g, int grp, DzFrag* dz0 = nullptr) {
@@ -785,7 +807,9 @@ __device__ __forceinline__ int2 f1a_body(const SfArgs& g, int grp, DzFrag* dz0 =
   // k_sf_f1: F1b's first W2^T half-chunk goes out now, into a buffer of its own behind the Xa images
   // (nothing of either phase aliases it), and lands under this epilogue; the barrier that ends F1a
   // waits for it, so F1b's first step starts from a landed buffer instead of a memory round trip
-  if constexpr (XOFF >= 0)
+  if constexpr (f1_ktile<KD, P, XOFF>())  // (the k-tile-major F1b: its chunk 0 is rows [0, 16) x all columns)
+    hc_dma_kt<W>(N.w2th, N.w2tl, 0, reinterpret_cast<_Float16*>(lds) + XOFF / 2 + W * XIMG, w, l);
+  else if constexpr (XOFF >= 0)
     hc_dma<W>(N.w2th, N.w2tl, 0, 0, reinterpret_cast<_Float16*>(lds) + XOFF / 2 + W * XIMG, w, l);
 
   // ---- H2^T = tanh(Z2^T + b2) (lane: rows n = 16 nt + 4g + i of column m = c); head
@@ -908,9 +932,9 @@ __device__ __forceinline__ int2 f1a_body(const SfArgs& g, int grp, DzFrag* dz0 =
       *reinterpret_cast<h8*>(dst + st * 1024) = hi;
       *reinterpret_cast<h8*>(dst + st * 1024 + 512) = lo;
       if constexpr (XOFF >= 0 && P == 3)  // (P == 1, the fp16 throughput mode: one register too many, F1b loads it)
-        if (st == 0) {
-          dz0->h = hi;
-          dz0->l = lo;
+        if (st == 0 || f1_ktile<KD, P, XOFF>()) {  // (k-tile-major F1b: the 64 accumulator registers become 64 of halves)
+          dz0[st].h = hi;
+          dz0[st].l = lo;
         }
     }
   }
@@ -1195,6 +1219,162 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   else f1b_body<1, KD, ND, W, P>(g, ng.y);
 }
 
+// ---- k-tile-major F1b of the fused kernel (KD = 16, three products).  f1b_body runs
+// `for n-step: for k-tile`, so no k-tile of dH1 is final before the last step and the whole dZ1 / dW1
+// epilogue (VALU) waits behind the loop (MFMA).  Each accumulator chain acc[kt] is independent of the
+// others, so the nest is swapped here: step kt runs the chain of k-tile kt alone (8 n-steps x 3
+// products, in f1b_body's order: dH1 and dZ1 keep their bits), and the epilogue of k-tile kt - 1 and
+// the workgroup sum of k-tile kt - 2 stand in the same step, independent of its MFMAs.  The operand
+// that stays resident is the tile's dZ2 (eight (hi, lo) fragments: 64 registers, handed over by F1a);
+// the accumulators are two tiles (8 registers) instead of 16.
+// Step kt's W2^T chunk is rows [16 kt, 16 kt + 16) x all 256 columns (hc_dma_kt), read by hc_frag(buf, s, ...).
+//
+// the dW1 slots of the k-tile-major F1b: [2][W][16 k][16 d] floats behind F1b's first W2^T chunk.  They
+// alias nothing (the chunk buffers, the W1a planes and the Xa images are all live during the loop); two,
+// because k-tile kt - 1 is stored in the step that sums k-tile kt - 2
+template <int W>
+constexpr int f1_kt_slot_bytes() { return 2 * W * 16 * 16 * 4; }
+
+template <int NET, int ND, int W, bool W1_KEPT, int XOFF>
+__device__ __forceinline__ void f1b_kt_body(const SfArgs& g, int grp, int edz, int ex, const DzFrag (&dz)[8]) {
+  constexpr int KD = 16, NTHR = 64 * W;
+  constexpr int SLOT = W * 16 * 16;  // floats per k-tile: [W][16 k][16 d]
+  static_assert(16 * ND <= NTHR, "one thread per (k, d) element of a k-tile's workgroup sum");
+  const SfNet& N = g.n[NET];
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  _Float16* sCh = reinterpret_cast<_Float16*>(lds);  // [2 buf][2 hi/lo][128][32]
+  _Float16* sW1 = sCh + 4 * H16;                      // [2 hi/lo][HID][KD]
+  const _Float16* sPre = reinterpret_cast<const _Float16*>(lds) + XOFF / 2 + W * XIMG;  // chunk 0, sent by F1a
+  float* sEp = lds + XOFF / 4 + W * XIMG / 2 + H16;   // behind the Xa images and sPre
+
+  int tid = threadIdx.x;  // (an opaque copy, as in f1b_body)
+  asm volatile("v_mov_b32 %0, %1" : "=v"(tid) : "v"(tid));
+  const int l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), c = l & 15, gq = l >> 4;
+  int tile = grp * W + w;
+  if (!dcheck(tile < g.M / 16, DC_SGD_TILE, tile)) tile = g.M / 16 - 1;
+  const int blk = grp;
+  FB_STAMP(0);
+  if constexpr (!W1_KEPT) w1_stage<KD, NTHR>(N, sW1, tid);  // (first read in step 1, behind step 0's barrier)
+  const float sgn = tile_sign(tile);
+  const _Float16* sX = reinterpret_cast<const _Float16*>(lds) + XOFF / 2 + w * XIMG;
+  h8 xh, xl;  // F1a's Xa fragment of the tile (Z1 recompute), and Xa^T for the dW1 product
+  xs_frag(sX, c, gq, xh, xl);
+  h4 xth, xtl;
+  xs_frag_t(sX, 0, c, gq, (tile & 1) ? 0x80008000u : 0u, xth, xtl);
+  const float k_z1 = sgn * N.sc[1] / pow2(ex) * SF_2LOG2E;
+  const int eu = 2 - ex - edz - (int)N.sc[5];  // u1 = sgn 2^(eu - ez), ez the k-tile's split exponent
+  const _Float16* w1b = sW1 + w1_off<KD>(c, gq & (KD / 8 - 1));
+  float* slot = sEp + (w * 16 + c) * 16 + 4 * (gq ^ ((c >> 1) & 3));  // (the quad swizzle of f1b_body's slots)
+
+  // the chain of k-tile kt: n-steps in order, the three products in mm16x3's order
+  auto chain = [&](const _Float16* buf) {
+    f4 a = f4zero();
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      h8 ch, cl;
+      hc_frag(buf, s, c, gq, ch, cl);
+      a = mm16x3(dz[s].h, dz[s].l, ch, cl, a);
+    }
+    return a;
+  };
+  // k-tile kt final: dZ1 = dH1 (1 - H1^2) (Z1 recomputed), split at the k-tile's own power of two (the
+  // wave max over its 16 x 16 block: a k-tile's dW1 rows are its own hidden units, so the scale is undone
+  // exactly, and it is never smaller than the whole tile's), dW1a^T = Xa^T dZ1 -> the wave's slot
+  auto epi = [&](int kt, f4 a, float* sl) {
+    const _Float16* q = w1b + kt * 16 * KD;
+    const h8 wh = *reinterpret_cast<const h8*>(q), wl = *reinterpret_cast<const h8*>(q + HID * KD);
+    const f4 z = mm16x3(xh, xl, wh, wl, f4zero());  // Z1 rows m = 4g + i, column k = 16 kt + c
+    float zmx = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float r = tanh_r(z[i] * k_z1);
+      a[i] *= fmaf(-r, r, r);
+      zmx = fmaxf(zmx, fabsf(a[i]));
+    }
+    const int ez = sf_exp(wave_max(zmx));  // (an all-zero k-tile: 0)
+    const float sz1 = pow2(ez), u1 = sgn * pow2(eu - ez), u1l = u1 * (1.f / 2048.f);
+    h4 zh, zl;  // (the lo half carried at 2^11, as in f1b_body)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float x = a[i] * sz1, X = x * 2048.f;
+      const _Float16 b = (_Float16)x;
+      zh[i] = b;
+      zl[i] = (_Float16)fmaf(-(float)b, 2048.f, X);
+    }
+    const f4 dh = mk16(xtl, zh, mk16(xth, zh, f4zero()));  // rows d = 4g + i, column k
+    const f4 dl2 = mk16(xth, zl, f4zero());
+    const float4 v = {fmaf(dl2[0], u1l, dh[0] * u1), fmaf(dl2[1], u1l, dh[1] * u1), fmaf(dl2[2], u1l, dh[2] * u1),
+                      fmaf(dl2[3], u1l, dh[3] * u1)};
+    *reinterpret_cast<float4*>(sl) = v;
+  };
+  // workgroup sum of k-tile kt (its slots are complete: a barrier after their stores), in wave order
+  auto wsum = [&](int kt, const float* se) {
+    if (tid < 16 * ND) {
+      const int kk = tid / ND, d = tid - kk * ND, k = 16 * kt + kk;
+      const int dq = 4 * (((d >> 2) & 3) ^ ((kk >> 1) & 3)) + (d & 3);
+      float sum = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < W; ++ww) sum += se[(ww * 16 + kk) * 16 + dq];
+      if (d < ND - 1) N.part_w1[((size_t)blk * HID + k) * (ND - 1) + d] = sum;
+      else N.part_b1[(size_t)blk * HID + k] = sum;
+    }
+  };
+  // A step's two halves are the chain (MFMA) and the epilogue (VALU).  Left to itself the compiler emits one
+  // after the other, sched_group_barrier pipelines did not change that, and waves in step after a barrier
+  // would all be in the same half.  So the waves of a SIMD (w, w + 4, w + 8, w + 12) take the halves in
+  // opposite orders, two and two: while two run MFMAs the other two run VALU work.  The halves are
+  // independent (different accumulators), so the order changes no bits.  Measured: worth only ~0.2% of c4
+  // on top of the loop itself, and a step still costs about its MFMA time plus its VALU time.
+  const bool early = (w >> 2) & 1;
+  auto step = [&](const _Float16* buf, int kp, f4 ap, float* sl) {
+    f4 a;
+    if (early) {
+      epi(kp, ap, sl);
+      __builtin_amdgcn_sched_barrier(0);
+      a = chain(buf);
+    } else {
+      a = chain(buf);
+      __builtin_amdgcn_sched_barrier(0);
+      epi(kp, ap, sl);
+    }
+    return a;
+  };
+  auto step_end = [&]() {
+    vm_drain();
+    __syncthreads();
+  };
+
+  // step 0 (chunk 0 landed before the barrier that ended F1a), step 1, then two steps a pass
+  FB_STAMP(1);
+  hc_dma_kt<W>(N.w2th, N.w2tl, 1, sCh + 2 * H16, w, l);
+  f4 a0 = chain(sPre);
+  step_end();
+  FB_STAMP(2);
+  hc_dma_kt<W>(N.w2th, N.w2tl, 2, sCh, w, l);
+  f4 a1 = step(sCh + 2 * H16, 0, a0, slot);
+  step_end();
+#pragma unroll 1
+  for (int kt = 2; kt < 16; kt += 2) {
+    wsum(kt - 2, sEp);
+    hc_dma_kt<W>(N.w2th, N.w2tl, kt + 1, sCh + 2 * H16, w, l);
+    a0 = step(sCh, kt - 1, a1, slot + SLOT);
+    step_end();
+    wsum(kt - 1, sEp + SLOT);
+    if (kt < 14) hc_dma_kt<W>(N.w2th, N.w2tl, kt + 2, sCh, w, l);
+    a1 = step(sCh + 2 * H16, kt, a0, slot);
+    step_end();
+    if (kt == 8) {
+      FB_STAMP(3);
+    }
+  }
+  FB_STAMP(4);
+  wsum(14, sEp);
+  epi(15, a1, slot + SLOT);
+  __syncthreads();
+  wsum(15, sEp + SLOT);
+  FB_STAMP(5);
+}
+
 // F1 fused (the default up to 4 actions, sf_f1_fused): F1a then F1b on the same 16-row tiles in one
 // workgroup.  The dZ2 hand-off is still written for F2, but F1b reads each lane's own fragments back
 // right after they were written (from the XCD's L2, not HBM), the tile exponent stays in a register,
@@ -1231,17 +1411,22 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   // the Xa images (xs_store) follow both nets' phase regions; up to 4 actions (at 8, forced by
   // RLKS_F1_FUSED=1, F1a's epilogue slots leave no room for them and F1b loads the X rows again)
   constexpr int XOFF = f1_x_kept<A_>() ? f1_lds_bytes<A_, KD, W>() : -1;
-  DzFrag dz0;
+  DzFrag dz[8];  // (f1b_body: the first one only)
+  constexpr bool KT = f1_ktile<KD, P, XOFF>();
   if (ng.x + g.net0 == 0) {
-    const int2 e = f1a_body<A_, 0, KD, W, P, XOFF>(g, ng.y, &dz0);
+    const int2 e = f1a_body<A_, 0, KD, W, P, XOFF>(g, ng.y, dz);
+    if constexpr (KT) vm_drain();  // F1b's first chunk (F1a's LDS-DMA) has landed, for every wave past the barrier
     __syncthreads();  // epilogue slots read; the dZ2 stores complete (the fence waits for them)
     asm volatile("" : "+s"(g2.x));
-    f1b_body<0, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<A_, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, &dz0);
+    if constexpr (KT) f1b_kt_body<0, 3 * A_ + 1, W, f1_w1_kept<A_, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, dz);
+    else f1b_body<0, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<A_, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, dz);
   } else {
-    const int2 e = f1a_body<1, 1, KD, W, P, XOFF>(g, ng.y, &dz0);
+    const int2 e = f1a_body<1, 1, KD, W, P, XOFF>(g, ng.y, dz);
+    if constexpr (KT) vm_drain();
     __syncthreads();
     asm volatile("" : "+s"(g2.x));
-    f1b_body<1, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<1, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, &dz0);
+    if constexpr (KT) f1b_kt_body<1, 3 * A_ + 1, W, f1_w1_kept<1, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, dz);
+    else f1b_body<1, KD, 3 * A_ + 1, W, P, true, f1_w1_kept<1, KD, W>(), XOFF>(g2, ng.y, e.x, e.y, dz);
   }
 }
 
@@ -1693,7 +1878,8 @@ static int launch_f1_net_p(SfArgs a, int net0, int nets, hipStream_t s, SfF1Form
   if (form == SF_F1_FUSED) {  // one fused kernel
     constexpr int WF = SF_F1F_W;
     launch_timed(KEV_F1A, k_sf_f1<A_, KD, WF, P>, dim3(a.M / (16 * WF) * nets), dim3(64 * WF),
-                 f1_lds_bytes<A_, KD, WF>() + (f1_x_kept<A_>() ? WF * XIMG * 2 + 2 * H16 * 2 : 0), s, a);
+                 f1_lds_bytes<A_, KD, WF>() + (f1_x_kept<A_>() ? WF * XIMG * 2 + 2 * H16 * 2 : 0) +
+                     (KD == 16 ? f1_kt_slot_bytes<WF>() : 0), s, a);
     RLKS_LAUNCHED();
     return RLKS_OK;
   }

@@ -82,14 +82,17 @@ def fwd_report(lib, tiles):
     print("first 12 waves (start, end, simd key):", [(int(start[i]), int(end[i]), int(k[i])) for i in order[:12]])
 
 
-def bwd_report(lib, tiles):
-    """F1b (f1b_body: k_sf_bwd, or the second half of the fused k_sf_f1) phases per wave; with the fused
+def bwd_report(lib, tiles, ktile=False):
+    """F1b (f1b_body: k_sf_bwd; f1b_kt_body: the second half of the fused k_sf_f1) phases per wave; with the fused
     kernel also the gap between F1a's last stamp and F1b's first, and a wave's whole F1 lifetime"""
     st = np.zeros((2, 8192, 8), np.uint64)
     assert lib.rlks_dbg_fb_stamps(st.ctypes.data_as(C.c_void_p)) == 0
     fa = np.zeros((2, 8192, 8), np.uint64)
     assert lib.rlks_dbg_fa_stamps(fa.ctypes.data_as(C.c_void_p)) == 0
     names = ["prologue", "dH1 loop", "Z1 + dZ1", "dZ1 exponent + Xa^T", "dW1 products + flush"]
+    if ktile:  # f1b_kt_body: a step is a k-tile's chain beside the previous k-tile's epilogue and the sum before it
+        names = ["constants, Xa fragments", "step 0 (chain alone)", "steps 1-9", "steps 10-15",
+                 "tail (epilogue 15, sums 14-15)"]
     for net in range(2):
         s = st[net, :tiles, :6].astype(np.int64)
         a = fa[net, :tiles, :7].astype(np.int64)
@@ -154,7 +157,9 @@ def main():
                   rows, grad.data_ptr(), None, ws.data_ptr(), ws.numel(), None)
     torch.cuda.synchronize()
     fwd_report(_lib.lib(), rows // 16)  # F1a (k_sf_fwd / k_sf_f1) phases, one wave per 16-row tile
-    bwd_report(_lib.lib(), rows // 16)  # F1b (k_sf_bwd / k_sf_f1)
+    # F1b (k_sf_bwd / k_sf_f1); the fused kernel's F1b at these shapes is the k-tile-major body unless the
+    # split kernels are forced
+    bwd_report(_lib.lib(), rows // 16, ktile=not os.environ.get("RLKS_F1_SPLIT", "").startswith("1"))
     f2_report(_lib.lib())
 
 if __name__ == "__main__":
