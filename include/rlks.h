@@ -266,7 +266,11 @@ typedef struct rlks_rollout_bufs {
 } rlks_rollout_bufs;
 
 /* T steps of (policy forward -> sample -> env step) into bufs, then the bootstrap values
- * V(obs[T]).  obs[0] must hold the current observations. */
+ * V(obs[T]).  obs[0] must hold the current observations.  On every rollout path (this one,
+ * rlks_rollout_ws at any precision and lane count, node-level or table env) actions[t] and logp[t] are
+ * bit for bit what rlks_sample_categorical gives for logits[t] and the lanes' own counters (global lane,
+ * episode, step), or rlks_sample_categorical_masked with the lanes' room masks under action masking:
+ * one draw function serves all of them. */
 int rlks_rollout(rlks_env* env, const rlks_mlp_desc* desc, const float* params_dev,
                  const rlks_rollout_bufs* bufs, int explore, void* stream);
 /* Policy / value forward with a workspace (rlks_ppo_workspace_bytes for >= n rows): required for
@@ -280,7 +284,8 @@ int rlks_absmax(const float* x, int rows, int cols, int ld, uint32_t* slot, void
 /* Same rollout; with desc->precision == RLKS_PRECISION_SF16 it runs the split-fp16 step kernel
  * (both nets' forward + sample + env step per launch, values written per step, V(obs[T]) last)
  * with the split weights in `workspace` (an rlks_ppo_workspace_bytes-sized buffer: the SGD step's
- * workspace can be shared).  Other precisions fall through to rlks_rollout. */
+ * workspace can be shared).  Other precisions fall through to rlks_rollout.  actions and logp are
+ * rlks_sample_categorical's on the stored logits here too (see rlks_rollout). */
 int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* desc, const float* params_dev,
                     const rlks_rollout_bufs* bufs, int explore, void* workspace, int64_t ws_bytes,
                     void* stream);

@@ -3,9 +3,10 @@
 // step (rlks_env_masked_sample) and the same draw under a caller's mask (rlks_sample_categorical_masked).
 //
 // A kernel of its own, like rules.hip: k_node_step_wl has no register to spare, and the room predicate is
-// the one k_rule_actions<RLKS_RULE_MYOPIC_WITH_ROOM> evaluates (integers; tests/rule_ref.has_room).  The
-// draw restates categorical() (env.hip) operation for operation on the masked row, so a row without a
-// masked entry gives that function's bits; the file is built without FMA contraction, as env.hip is.
+// has_room() (env_device.h), which k_rule_actions<RLKS_RULE_MYOPIC_WITH_ROOM> evaluates too.  The masked
+// draw follows categorical() (env_device.h) operation for operation on the masked row, so a row without a
+// masked entry gives that function's bits; it differs in its fallback index and in writing the masked row
+// back, so it stays a function of its own.  The file is built without FMA contraction, as env.hip is.
 #include <hip/hip_runtime.h>
 
 #include "env_device.h"
@@ -20,12 +21,8 @@ __device__ __forceinline__ uint64_t room_mask(const EnvView& v, int lane) {
   const int C = v.C;
   if (v.nodes <= 0) return low_bits(C);
   uint64_t m = 0;
-  for (int c = 0; c < C; ++c) {
-    // the cluster's nodes are equally sized: room on some node <=> fewer pods than its nodes hold
-    const int pods = v.used_cpu[(size_t)c * v.N + lane] / v.pod_cpu;
-    const int cap = v.nodes * min(v.cap[c] / v.pod_cpu, v.cap[C + c] / v.pod_mem);
-    if (pods < cap) m |= 1ull << c;
-  }
+  for (int c = 0; c < C; ++c)
+    if (has_room(v, lane, c)) m |= 1ull << c;
   return m ? m : low_bits(C);
 }
 
@@ -79,10 +76,9 @@ __global__ void __launch_bounds__(ENV_BLOCK) k_masked_sample(EnvView v, float* _
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= v.N) return;
   const uint64_t m = room_mask(v, lane);
-  const u32x4 ctr{(uint32_t)(v.env_offset + lane), (uint32_t)v.episode[lane], (uint32_t)v.step[lane],
-                  (uint32_t)RLKS_PURPOSE_ACTION << 16};
   float lp;
-  actions[lane] = categorical_masked(logits + (size_t)lane * v.C, v.C, m, explore != 0, ctr, v.k0, v.k1, lp);
+  actions[lane] = categorical_masked(logits + (size_t)lane * v.C, v.C, m, explore != 0,
+                                     action_ctr(v, lane, v.episode[lane], v.step[lane]), v.k0, v.k1, lp);
   logp[lane] = lp;
   if (mask_out) mask_out[lane] = m;
 }
@@ -97,12 +93,8 @@ __global__ void __launch_bounds__(256) k_sample_categorical_masked(float* __rest
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float lp;
-  u32x4 ctr{0u, 0u, 0u, (uint32_t)RLKS_PURPOSE_ACTION << 16};
-  if (explore) {  // ids may be NULL for argmax
-    ctr.x = ids[3 * i];
-    ctr.y = ids[3 * i + 1];
-    ctr.z = ids[3 * i + 2];
-  }
+  u32x4 ctr = action_ctr(0u, 0u, 0u);
+  if (explore) ctr = action_ctr(ids[3 * i], ids[3 * i + 1], ids[3 * i + 2]);  // ids may be NULL for argmax
   actions[i] = categorical_masked(logits + (size_t)i * A, A, mask[i], explore != 0, ctr, k0, k1, lp);
   if (logp) logp[i] = lp;
 }

@@ -551,33 +551,7 @@ __device__ __forceinline__ bool depart_any(const EnvView& v, const uint32_t* S, 
   return !u_below_S(v, S, P, x.x, lg1p);
 }
 
-// TorchCategorical over the A logits l[0..A): explore -> u = f32(u53(Philox(ctr, key) words 0, 1)) *
-// sum exp(l - max), the first a with u < cumsum; else argmax.  logp of the choice.  Shared by the
-// rollout's fused sample + step and the standalone sampler (oracle.sample_actions restates it).
-__device__ __forceinline__ int categorical(const float* __restrict__ l, int A, bool explore, u32x4 ctr, uint32_t k0,
-                                          uint32_t k1, float& logp) {
-  float mx = l[0];
-  int amax = 0;
-  for (int a = 1; a < A; ++a)
-    if (l[a] > mx) { mx = l[a]; amax = a; }
-  float s = 0.f;
-  for (int a = 0; a < A; ++a) s += expf(l[a] - mx);
-  int act = amax;
-  if (explore) {
-    const u32x4 x = philox4x32_10(ctr, k0, k1);
-    const float u = (float)u53(x.x, x.y) * s;
-    float c = 0.f;
-    act = A - 1;
-    for (int a = 0; a < A; ++a) {
-      c += expf(l[a] - mx);
-      if (u < c) { act = a; break; }
-    }
-  }
-  logp = l[act] - mx - logf(s);
-  return act;
-}
-
-// categorical() over the 2^cs contiguous lanes of a wave that hold one env's (env, cluster) pairs:
+// categorical() (env_device.h) over the 2^cs contiguous lanes of a wave that hold one env's (env, cluster) pairs:
 // lane c of the group brings its own logit l (lanes c >= A: any value, never read), every lane of
 // the group returns the same action and logp.  Bit for bit categorical()'s results for logits
 // without NaNs: the maximum is the lowest-index one's own bits, each lane takes one
@@ -679,10 +653,7 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
         ep[j] = v.episode[lane];
         l = logits[(size_t)lane * C + c];
       }
-      a[j] = categorical_lanes(l, c, cs, C, explore != 0,
-                               u32x4{(uint32_t)(v.env_offset + lane), (uint32_t)ep[j], (uint32_t)t[j],
-                                     (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                               v.k0, v.k1, lp);
+      a[j] = categorical_lanes(l, c, cs, C, explore != 0, action_ctr(v, lane, ep[j], t[j]), v.k0, v.k1, lp);
       if (in && c == 0) {
         actions_out[lane] = a[j];
         logp[lane] = lp;
@@ -872,10 +843,7 @@ __global__ void __launch_bounds__(256) k_node_step(EnvView v, const double* __re
     int a;
     if constexpr (SAMPLE) {
       float lp;
-      a = categorical(logits + (size_t)lane * C, C, explore != 0,
-                      u32x4{(uint32_t)(v.env_offset + lane), (uint32_t)ep, (uint32_t)t,
-                            (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                      v.k0, v.k1, lp);
+      a = categorical(logits + (size_t)lane * C, C, explore != 0, action_ctr(v, lane, ep, t), v.k0, v.k1, lp);
       actions_out[lane] = a;
       logp[lane] = lp;
     } else {
@@ -941,12 +909,8 @@ __global__ void k_sample_categorical(const float* __restrict__ logits, int n, in
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float lp;
-  u32x4 ctr{0u, 0u, 0u, (uint32_t)RLKS_PURPOSE_ACTION << 16};
-  if (explore) {  // ids may be NULL for argmax
-    ctr.x = ids[3 * i];
-    ctr.y = ids[3 * i + 1];
-    ctr.z = ids[3 * i + 2];
-  }
+  u32x4 ctr = action_ctr(0u, 0u, 0u);
+  if (explore) ctr = action_ctr(ids[3 * i], ids[3 * i + 1], ids[3 * i + 2]);  // ids may be NULL for argmax
   actions[i] = categorical(logits + (size_t)i * A, A, explore != 0, ctr, k0, k1, lp);
   if (logp) logp[i] = lp;
 }
@@ -960,10 +924,9 @@ __global__ void k_sample_step(EnvView v, const double* __restrict__ cost, const 
   stage_tables(s_tab, cost, lat, v.T * v.C);
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= v.N) return;
-  const u32x4 ctr{(uint32_t)(v.env_offset + lane), (uint32_t)v.episode[lane], (uint32_t)v.step[lane],
-                  (uint32_t)RLKS_PURPOSE_ACTION << 16};
   float lp;
-  const int act = categorical(logits + (size_t)lane * v.C, v.C, explore != 0, ctr, v.k0, v.k1, lp);
+  const int act = categorical(logits + (size_t)lane * v.C, v.C, explore != 0,
+                              action_ctr(v, lane, v.episode[lane], v.step[lane]), v.k0, v.k1, lp);
   actions[lane] = act;
   logp[lane] = lp;
   StepOut r = step_lane(v, s_tab, lane, act, obs + (size_t)lane * 3 * v.C, nullptr);

@@ -149,6 +149,85 @@ __device__ __forceinline__ double noise(const EnvView& v, int lane, int t, int c
   return __dadd_rn(v.cpu_lo, __dmul_rn(v.span, u));
 }
 
+// ---------------------------------------------------------------- the action draw
+// One definition each of the draw's Philox counter and of TorchCategorical over one row, for every
+// kernel that samples.  Both forms of the draw round every operation on its own in
+// whichever file includes them, so an action and its logp depend on the row and the counter alone, never
+// on the kernel that drew.  That takes contract(off) in the body and exp / log as the builtins, called
+// from inside that scope: the compiler expands them in place with the caller's contraction setting (expf()
+// / logf() are header functions that carry the file's, under which log's last multiply and add fuse).
+
+// counter of the action draw of global lane `gid` at (episode, step); the key is the env's seed
+__device__ __forceinline__ u32x4 action_ctr(uint32_t gid, uint32_t episode, uint32_t step) {
+  return u32x4{gid, episode, step, (uint32_t)RLKS_PURPOSE_ACTION << 16};
+}
+__device__ __forceinline__ u32x4 action_ctr(const EnvView& v, int lane, int episode, int step) {
+  return action_ctr((uint32_t)(v.env_offset + lane), (uint32_t)episode, (uint32_t)step);
+}
+
+// TorchCategorical over the A logits l[0..A): explore -> u = f32(u53(Philox(ctr, key) words 0, 1)) *
+// sum exp(l - max), the first a with u < cumsum; else argmax.  logp of the choice.  Shared by the
+// rollout's fused sample + step and the standalone sampler (oracle.sample_actions restates it).
+__device__ __forceinline__ int categorical(const float* __restrict__ l, int A, bool explore, u32x4 ctr, uint32_t k0,
+                                          uint32_t k1, float& logp) {
+#pragma clang fp contract(off)
+  float mx = l[0];
+  int amax = 0;
+  for (int a = 1; a < A; ++a)
+    if (l[a] > mx) { mx = l[a]; amax = a; }
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) s += __builtin_expf(l[a] - mx);
+  int act = amax;
+  if (explore) {
+    const u32x4 x = philox4x32_10(ctr, k0, k1);
+    const float u = (float)u53(x.x, x.y) * s;
+    float c = 0.f;
+    act = A - 1;
+    for (int a = 0; a < A; ++a) {
+      c += __builtin_expf(l[a] - mx);
+      if (u < c) { act = a; break; }
+    }
+  }
+  logp = l[act] - mx - __builtin_logf(s);
+  return act;
+}
+
+// categorical() over a row held in registers (A_ known at compile time), for the kernels whose head
+// leaves the logits there: every loop unrolled, each expf(l[a] - mx) taken once and kept, no early
+// exit from the search (a `found` flag), l[act] picked by select so that the row is never indexed
+// by a runtime value.  The same operations in the same order on the same values, so the same bits.
+template <int A_>
+__device__ __forceinline__ int categorical_row(const float (&l)[A_], bool explore, u32x4 ctr, uint32_t k0, uint32_t k1,
+                                               float& logp) {
+#pragma clang fp contract(off)
+  float mx = l[0];
+  int amax = 0;
+#pragma unroll
+  for (int a = 1; a < A_; ++a)
+    if (l[a] > mx) { mx = l[a]; amax = a; }
+  float e[A_], s = 0.f;
+#pragma unroll
+  for (int a = 0; a < A_; ++a) { e[a] = __builtin_expf(l[a] - mx); s += e[a]; }
+  int act = amax;
+  if (explore) {
+    const u32x4 x = philox4x32_10(ctr, k0, k1);
+    const float u = (float)u53(x.x, x.y) * s;
+    float c = 0.f;
+    act = A_ - 1;
+    bool found = false;
+#pragma unroll
+    for (int a = 0; a < A_; ++a) {
+      c += e[a];
+      if (!found && u < c) { act = a; found = true; }
+    }
+  }
+  float la = l[0];
+#pragma unroll
+  for (int a = 0; a < A_; ++a) la = (a == act) ? l[a] : la;
+  logp = la - mx - __builtin_logf(s);
+  return act;
+}
+
 // ---------------------------------------------------------------- node-level extension
 // DESIGN.md §4 (builder-defined; same algorithm and the same Philox counters as
 // oracle/rlks_oracle.c).  Node state is int2 {free cpu, free mem}, [env][C][N]: each lane walks
@@ -162,6 +241,15 @@ __device__ __forceinline__ size_t node_off(size_t g) { return g; }
 __device__ __forceinline__ int chunk_stride(int nodes) { return ((nodes >> 3) + 7) & ~7; }
 __device__ __forceinline__ uint16_t* chunk_tot(const EnvView& v, int lane, int c) {
   return v.chunk + ((size_t)lane * v.C + c) * chunk_stride(v.nodes);
+}
+
+// whether cluster c of `lane` can take one more pod (the action mask's bit and MYOPIC_WITH_ROOM's filter;
+// tests/rule_ref.has_room).  The cluster's nodes are equally sized: room on some node <=> fewer pods
+// than its nodes hold.
+__device__ __forceinline__ bool has_room(const EnvView& v, int lane, int c) {
+  const int pods = v.used_cpu[(size_t)c * v.N + lane] / v.pod_cpu;
+  const int cap = v.nodes * min(v.cap[c] / v.pod_cpu, v.cap[v.C + c] / v.pod_mem);
+  return pods < cap;
 }
 
 // initial occupancy of cluster c for one lane (episode `episode`); col = node_col(lane) + c*N,

@@ -128,6 +128,69 @@ __device__ __forceinline__ VfRow vf_row(float v, float vt, float vf_clip, float 
   const bool in = sq <= vf_clip;
   return {in ? vf_coeff * 2.f * diff * inv_count : 0.f, fminf(sq, vf_clip), in ? (double)diff + (double)err : 0.0};
 }
+
+// PPO's policy loss of one row in fp32 (RLlib ppo_torch_policy semantics), beside vf_row:
+// out = the row's logits, lo = the A_ logits it was sampled from, adv_raw / logp_old / act_f = the
+// record's advantage, old log-prob and action as stored (floats), adv_mean / adv_invstd / klc /
+// inv_count = the step's dyn scalars.  dl = dL/dlogits already over the row count; returns the row's
+// policy-loss, KL and entropy terms.
+// The advantage is standardised and the action converted here, not by the caller: with them ahead of
+// the call the 8-action split-fp16 F1 kernels, which sit at 128 registers, spill.
+// KLC_FUSED: dr * (..) + klc * (..) is one rounded product and one FMA, and the two loss heads have
+// always differed in which (the compiler's choice, which followed from where each loaded klc): the
+// split-fp16 kernels fuse klc's product (true), the fp32 head dr's (false).  Written out so that each
+// keeps its bits whatever the compiler would pick (profiles/r15_shared_rows).
+struct PiRow {
+  float pl, kl, ent;
+};
+template <int A_, bool KLC_FUSED>
+__device__ __forceinline__ PiRow pi_row(const float (&out)[A_], const float* lo, float adv_raw, float logp_old,
+                                        float act_f, const rlks_ppo_coeffs& co, float adv_mean, float adv_invstd,
+                                        float klc, float inv_count, float (&dl)[A_]) {
+  const float adv = (adv_raw - adv_mean) * adv_invstd;
+  const int act = (int)act_f;
+  // a masked action (old logit <= RLKS_MASKED_LOGIT_MAX, rlks_env_masked_sample) keeps its old logit: its
+  // probability, KL, entropy and gradient terms are then exact zeros
+  float lg[A_];
+#pragma unroll
+  for (int a = 0; a < A_; ++a) lg[a] = lo[a] <= RLKS_MASKED_LOGIT_MAX ? lo[a] : out[a];
+  float mx = lg[0], mo = lo[0];
+#pragma unroll
+  for (int a = 1; a < A_; ++a) { mx = fmaxf(mx, lg[a]); mo = fmaxf(mo, lo[a]); }
+  float se = 0.f, so = 0.f;
+#pragma unroll
+  for (int a = 0; a < A_; ++a) { se += expf(lg[a] - mx); so += expf(lo[a] - mo); }
+  const float lse = mx + logf(se), lso = mo + logf(so);
+  float p[A_], lp[A_], po[A_];
+  float kl = 0.f, ent = 0.f, lpa = 0.f;
+#pragma unroll
+  for (int a = 0; a < A_; ++a) {
+    lp[a] = lg[a] - lse;
+    p[a] = expf(lp[a]);
+    const float lpo = lo[a] - lso;
+    po[a] = expf(lpo);
+    kl += po[a] * (lpo - lp[a]);
+    ent -= p[a] * lp[a];
+    lpa = (a == act) ? lp[a] : lpa;
+  }
+  const float ratio = expf(lpa - logp_old);
+  const float lo_c = 1.f - co.clip_param, hi_c = 1.f + co.clip_param;
+  const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
+  const float s1 = adv * ratio, s2 = adv * rc;
+  // torch.min backward splits ties evenly; torch.clamp passes the gradient on [lo, hi]
+  const float w1 = s1 < s2 ? 1.f : (s1 == s2 ? 0.5f : 0.f);
+  const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
+  const float dr = -adv * (w1 + (1.f - w1) * inr) * ratio;  // dL / dlogp(act)
+#pragma unroll
+  for (int a = 0; a < A_; ++a) {
+    const float da = (a == act ? 1.f : 0.f) - p[a], dk = p[a] - po[a];
+    float d = KLC_FUSED ? fmaf(klc, dk, dr * da) : fmaf(dr, da, klc * dk);
+    d += co.entropy_coeff * p[a] * (lp[a] + ent);
+    dl[a] = d * inv_count;
+  }
+  return {-fminf(s1, s2), kl, ent};
+}
+
 // the bias gradient's per-block partial from a block's f64 sum of ex, as an exact hi + lo pair of
 // floats (both summed by the f64 reduce)
 __device__ __forceinline__ void vf_b3_part(double sum_ex, float vf_coeff, float inv_count, float* part2) {

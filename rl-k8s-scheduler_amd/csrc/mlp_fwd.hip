@@ -181,38 +181,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_fwd_head(FwdArgs g) {
     } else if (MODE == FWD_ROLLOUT) {
       if (m < g.M) {
         // TorchCategorical: sample (Philox, counter = lane/episode/step) or argmax (explore=False)
-        float mx = out[0];
-        int amax = 0;
-#pragma unroll
-        for (int a = 1; a < A_; ++a)
-          if (out[a] > mx) { mx = out[a]; amax = a; }
-        float e[A_], se = 0.f;
-#pragma unroll
-        for (int a = 0; a < A_; ++a) { e[a] = expf(out[a] - mx); se += e[a]; }
-        int act = amax;
         const EnvView& v = g.env;
-        if (g.explore) {
-          const u32x4 x = philox4x32_10(u32x4{(uint32_t)(v.env_offset + m), (uint32_t)v.episode[m],
-                                              (uint32_t)v.step[m], (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                                        v.k0, v.k1);
-          const float u = (float)u53(x.x, x.y) * se;
-          float c = 0.f;
-          act = A_ - 1;
-          bool found = false;
+        float lp;
+        const int act = categorical_row<A_>(out, g.explore != 0, action_ctr(v, m, v.episode[m], v.step[m]), v.k0,
+                                            v.k1, lp);
 #pragma unroll
-          for (int a = 0; a < A_; ++a) {
-            c += e[a];
-            if (!found && u < c) { act = a; found = true; }
-          }
-        }
-        float la = out[0];
-#pragma unroll
-        for (int a = 0; a < A_; ++a) {
-          g.out[(size_t)m * A_ + a] = out[a];
-          la = (a == act) ? out[a] : la;
-        }
+        for (int a = 0; a < A_; ++a) g.out[(size_t)m * A_ + a] = out[a];
         g.actions[m] = act;
-        g.logp[m] = la - mx - logf(se);
+        g.logp[m] = lp;
         const StepOut r = step_lane(v, sTab, m, act, g.obs_next + (size_t)m * D, nullptr);
         g.rewards[m] = (float)r.reward;
         g.dones[m] = (uint8_t)r.done;
@@ -226,53 +202,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_fwd_head(FwdArgs g) {
         const float inv_count = g.dyn[RLKS_DYN_INV_COUNT];
         const int Ap = g.A_pi;
         if (NET == 0) {
-          const float* lo = rec + D;
-          const float adv = (rec[D + Ap] - g.dyn[RLKS_DYN_ADV_MEAN]) * g.dyn[RLKS_DYN_ADV_INVSTD];
-          const float logp_old = rec[D + Ap + 2];
-          const int act = (int)rec[D + Ap + 3];
-          // a masked action (old logit <= RLKS_MASKED_LOGIT_MAX, rlks_env_masked_sample) keeps its old
-          // logit: its probability, KL, entropy and gradient terms are then exact zeros
-          float lg[A_];
-#pragma unroll
-          for (int a = 0; a < A_; ++a) lg[a] = lo[a] <= RLKS_MASKED_LOGIT_MAX ? lo[a] : out[a];
-          float mx = lg[0], mo = lo[0];
-#pragma unroll
-          for (int a = 1; a < A_; ++a) { mx = fmaxf(mx, lg[a]); mo = fmaxf(mo, lo[a]); }
-          float se = 0.f, so = 0.f;
-#pragma unroll
-          for (int a = 0; a < A_; ++a) { se += expf(lg[a] - mx); so += expf(lo[a] - mo); }
-          const float lse = mx + logf(se), lso = mo + logf(so);
-          float p[A_], lp[A_], po[A_];
-          float kl = 0.f, ent = 0.f, lpa = 0.f;
-#pragma unroll
-          for (int a = 0; a < A_; ++a) {
-            lp[a] = lg[a] - lse;
-            p[a] = expf(lp[a]);
-            const float lpo = lo[a] - lso;
-            po[a] = expf(lpo);
-            kl += po[a] * (lpo - lp[a]);
-            ent -= p[a] * lp[a];
-            lpa = (a == act) ? lp[a] : lpa;
-          }
-          const float ratio = expf(lpa - logp_old);
-          const float lo_c = 1.f - g.co.clip_param, hi_c = 1.f + g.co.clip_param;
-          const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-          const float s1 = adv * ratio, s2 = adv * rc;
-          // torch.min backward splits ties evenly; torch.clamp passes the gradient on [lo, hi]
-          const float w1 = s1 < s2 ? 1.f : (s1 == s2 ? 0.5f : 0.f);
-          const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-          const float dr = -adv * (w1 + (1.f - w1) * inr) * ratio;  // dL / dlogp(act)
-          const float klc = g.dyn[RLKS_DYN_KL_COEFF];
-#pragma unroll
-          for (int a = 0; a < A_; ++a) {
-            float d = dr * ((a == act ? 1.f : 0.f) - p[a]);
-            d += klc * (p[a] - po[a]);
-            d += g.co.entropy_coeff * p[a] * (lp[a] + ent);
-            dl[a] = d * inv_count;
-          }
-          st_pl = -fminf(s1, s2);
-          st_kl = kl;
-          st_ent = ent;
+          const PiRow p = pi_row<A_, false>(out, rec + D, rec[D + Ap], rec[D + Ap + 2], rec[D + Ap + 3], g.co,
+                                            g.dyn[RLKS_DYN_ADV_MEAN], g.dyn[RLKS_DYN_ADV_INVSTD],
+                                            g.dyn[RLKS_DYN_KL_COEFF], inv_count, dl);
+          st_pl = p.pl;
+          st_kl = p.kl;
+          st_ent = p.ent;
         } else {
           const VfRow v = vf_row(out[0], rec[D + Ap + 1], g.co.vf_clip_param, g.co.vf_loss_coeff, inv_count);
           st_vf = v.sq;

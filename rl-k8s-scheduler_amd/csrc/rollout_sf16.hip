@@ -244,35 +244,12 @@ __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
         for (int a = 0; a < A_; ++a) g.logits[(tN + m) * A_ + a] = lg[a];
       if (MODE == FWD_ROLLOUT) {
         // TorchCategorical: sample (Philox, counter = lane / episode / step) or argmax (explore = 0)
-        float mx = lg[0];
-        int amax = 0;
-#pragma unroll
-        for (int a = 1; a < A_; ++a)
-          if (lg[a] > mx) { mx = lg[a]; amax = a; }
-        float ex[A_], se = 0.f;
-#pragma unroll
-        for (int a = 0; a < A_; ++a) { ex[a] = expf(lg[a] - mx); se += ex[a]; }
-        int act = amax;
         const EnvView& v = g.env;
-        if (g.explore) {
-          const u32x4 x = philox4x32_10(u32x4{(uint32_t)(v.env_offset + m), (uint32_t)v.episode[m],
-                                              (uint32_t)v.step[m], (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                                        v.k0, v.k1);
-          const float u = (float)u53(x.x, x.y) * se;
-          float c = 0.f;
-          act = A_ - 1;
-          bool found = false;
-#pragma unroll
-          for (int a = 0; a < A_; ++a) {
-            c += ex[a];
-            if (!found && u < c) { act = a; found = true; }
-          }
-        }
-        float la = lg[0];
-#pragma unroll
-        for (int a = 0; a < A_; ++a) la = (a == act) ? lg[a] : la;
+        float lp;
+        const int act = categorical_row<A_>(lg, g.explore != 0, action_ctr(v, m, v.episode[m], v.step[m]), v.k0, v.k1,
+                                            lp);
         g.actions[tN + m] = act;
-        g.logp[tN + m] = la - mx - logf(se);
+        g.logp[tN + m] = lp;
         // next observation straight into this lane's LDS row, then to obs[t + 1] in HBM
         float* o = sObs + r * KD;
         const StepOut so = step_lane(v, sTab, m, act, o, nullptr);

@@ -47,21 +47,14 @@ __global__ void __launch_bounds__(ENV_BLOCK) k_rule_actions(EnvView v, const flo
     for (int c = 0; c < C; ++c) {
       const double s = __dadd_rn(__dmul_rn(v.w_cost, (double)o[c]), __dmul_rn(v.w_lat, (double)o[C + c]));
       if (c == 0 || s > best) { best = s; act = c; }
-      if (filter) {
-        // the cluster's nodes are equally sized: room on some node <=> fewer pods than its nodes hold
-        const int pods = v.used_cpu[(size_t)c * v.N + lane] / v.pod_cpu;
-        const int cap = v.nodes * min(v.cap[c] / v.pod_cpu, v.cap[C + c] / v.pod_mem);
-        if (pods < cap && (act_room < 0 || s > best_room)) { best_room = s; act_room = c; }
-      }
+      if (filter && has_room(v, lane, c) && (act_room < 0 || s > best_room)) { best_room = s; act_room = c; }
     }
     if (act_room >= 0) act = act_room;
   } else {  // RLKS_RULE_RANDOM
-    // categorical() (env.hip) on an all-zero logits row: max 0, every expf(0 - 0) = 1, their sum in
+    // categorical() (env_device.h) on an all-zero logits row: max 0, every expf(0 - 0) = 1, their sum in
     // index order = (float)C exactly, u = f32(u53) * C, the first a with u < a + 1 (else C - 1), i.e.
     // floor(u) capped at C - 1 (u53 can round to 1.0f)
-    const u32x4 x = philox4x32_10(u32x4{(uint32_t)(v.env_offset + lane), (uint32_t)v.episode[lane],
-                                        (uint32_t)v.step[lane], (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                                  v.k0, v.k1);
+    const u32x4 x = philox4x32_10(action_ctr(v, lane, v.episode[lane], v.step[lane]), v.k0, v.k1);
     const float u = (float)u53(x.x, x.y) * (float)C;
     act = min((int)u, C - 1);
   }

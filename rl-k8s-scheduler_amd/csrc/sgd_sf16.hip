@@ -343,53 +343,11 @@ __device__ __forceinline__ void sf_loss_t(const SfArgs& g, const LossDyn& dy, co
   st[0] = st[1] = st[2] = st[3] = 0.f;
   vex = 0.0;
   if (NET == 0) {
-    const float* lo = r.lo;
-    const float adv = (r.adv - dy.adv_mean) * dy.adv_invstd;
-    const float logp_old = r.lpo;
-    const int act = (int)r.act;
-    // a masked action (old logit <= RLKS_MASKED_LOGIT_MAX, rlks_env_masked_sample) keeps its old logit: its
-    // probability, KL, entropy and gradient terms are then exact zeros
-    float lg[A_];
-#pragma unroll
-    for (int a = 0; a < A_; ++a) lg[a] = lo[a] <= RLKS_MASKED_LOGIT_MAX ? lo[a] : out[a];
-    float mx = lg[0], mo = lo[0];
-#pragma unroll
-    for (int a = 1; a < A_; ++a) { mx = fmaxf(mx, lg[a]); mo = fmaxf(mo, lo[a]); }
-    float se = 0.f, so = 0.f;
-#pragma unroll
-    for (int a = 0; a < A_; ++a) { se += expf(lg[a] - mx); so += expf(lo[a] - mo); }
-    const float lse = mx + logf(se), lso = mo + logf(so);
-    float p[A_], lp[A_], po[A_];
-    float kl = 0.f, ent = 0.f, lpa = 0.f;
-#pragma unroll
-    for (int a = 0; a < A_; ++a) {
-      lp[a] = lg[a] - lse;
-      p[a] = expf(lp[a]);
-      const float lpo = lo[a] - lso;
-      po[a] = expf(lpo);
-      kl += po[a] * (lpo - lp[a]);
-      ent -= p[a] * lp[a];
-      lpa = (a == act) ? lp[a] : lpa;
-    }
-    const float ratio = expf(lpa - logp_old);
-    const float lo_c = 1.f - g.co.clip_param, hi_c = 1.f + g.co.clip_param;
-    const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-    const float s1 = adv * ratio, s2 = adv * rc;
-    // torch.min backward splits ties evenly; torch.clamp passes the gradient on [lo, hi]
-    const float w1 = s1 < s2 ? 1.f : (s1 == s2 ? 0.5f : 0.f);
-    const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-    const float dr = -adv * (w1 + (1.f - w1) * inr) * ratio;
-    const float klc = dy.klc;
-#pragma unroll
-    for (int a = 0; a < A_; ++a) {
-      float d = dr * ((a == act ? 1.f : 0.f) - p[a]);
-      d += klc * (p[a] - po[a]);
-      d += g.co.entropy_coeff * p[a] * (lp[a] + ent);
-      dl[a] = d * inv_count;
-    }
-    st[0] = -fminf(s1, s2);
-    st[2] = kl;
-    st[3] = ent;
+    const PiRow p = pi_row<A_, true>(out, r.lo, r.adv, r.lpo, r.act, g.co, dy.adv_mean, dy.adv_invstd, dy.klc,
+                                     inv_count, dl);
+    st[0] = p.pl;
+    st[2] = p.kl;
+    st[3] = p.ent;
   } else {
     const VfRow v = vf_row(out[0], r.vt, g.co.vf_clip_param, g.co.vf_loss_coeff, inv_count);
     st[1] = v.sq;

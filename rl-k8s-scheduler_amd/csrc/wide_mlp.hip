@@ -76,7 +76,7 @@ WideWs wide_ws_layout(int D, int H, int A, int M, char* base) {
 bool wide_needed(const rlks_mlp_desc* d) { return d->hidden != HID || d->n_actions > 8 || d->obs_dim + 1 > 32; }
 
 // ----------------------------------------------------------------------------- kernels
-// PPO loss per row (same math as sgd_sf16.hip's sf_loss, for up to 64 actions); dout -> HBM, per-block
+// PPO loss per row (the math of pi_row / vf_row, mlp_common.h, for up to 64 actions); dout -> HBM, per-block
 // stats [policy loss, vf loss, kl, entropy], max |dout| -> slot.  Value net: one thread per row.
 __global__ __launch_bounds__(LOSS_ROWS) void k_wide_loss_vf(const float* __restrict__ out, const float* __restrict__ x,
                                                           int stride, int M, int D, int A, rlks_ppo_coeffs co,
@@ -241,34 +241,16 @@ __global__ void k_wide_stats(const float* __restrict__ ps_pi, const float* __res
   }
 }
 
-// TorchCategorical over A logits for every lane (Philox counter = lane / episode / step, as the
-// fused rollout kernels): action and its log-probability
+// categorical() (env_device.h) over A logits for every lane, with the lane's own counter: action and
+// its log-probability
 __global__ void k_wide_sample(EnvView v, const float* __restrict__ logits, int A, int explore,
                               int32_t* __restrict__ actions, float* __restrict__ logp) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= v.N) return;
-  const float* lg = logits + (size_t)m * A;
-  float mx = lg[0];
-  int amax = 0;
-  for (int a = 1; a < A; ++a)
-    if (lg[a] > mx) { mx = lg[a]; amax = a; }
-  float se = 0.f;
-  for (int a = 0; a < A; ++a) se += expf(lg[a] - mx);
-  int act = amax;
-  if (explore) {
-    const u32x4 x = philox4x32_10(u32x4{(uint32_t)(v.env_offset + m), (uint32_t)v.episode[m], (uint32_t)v.step[m],
-                                        (uint32_t)RLKS_PURPOSE_ACTION << 16},
-                                  v.k0, v.k1);
-    const float u = (float)u53(x.x, x.y) * se;
-    float c = 0.f;
-    act = A - 1;
-    for (int a = 0; a < A; ++a) {
-      c += expf(lg[a] - mx);
-      if (u < c) { act = a; break; }
-    }
-  }
-  actions[m] = act;
-  logp[m] = lg[act] - mx - logf(se);
+  float lp;
+  actions[m] = categorical(logits + (size_t)m * A, A, explore != 0, action_ctr(v, m, v.episode[m], v.step[m]), v.k0,
+                           v.k1, lp);
+  logp[m] = lp;
 }
 
 // dZ2 = (dout W3) (1 - H2^2), K = the head's outputs (64 / 1): too short a reduction for the split

@@ -210,40 +210,66 @@ def test_python_sample_step():
         Q.sample_step(torch.zeros(case.n, case.C, device=d))
 
 
-@pytest.mark.parametrize("C,nodes,H,N,T,mb", [
-    (8, 16, 256, 520, 16, 8192),   # split-fp16, node_rollout
-    (16, 32, 384, 136, 8, 1024),   # hidden 384: wide_rollout
+SF_ROLL_FUSED_MAX_LANES = 16384  # (ppo.hip) above it a split-fp16 table rollout runs k_sf_fwd16 + k_sample_step per step
+
+
+def _row(C, nodes, H, N, T, mb, rows=100, prec="auto", per_step=False, explore=True, id=None):
+    return pytest.param(C, nodes, H, N, T, mb, rows, prec, per_step, explore, id=id)
+
+
+@pytest.mark.parametrize("C,nodes,H,N,T,mb,rows,prec,per_step,explore", [
+    _row(8, 16, 256, 520, 16, 8192, id="8-16-256-520-16-8192"),   # split-fp16, node_rollout
+    _row(16, 32, 384, 136, 8, 1024, id="16-32-384-136-8-1024"),   # hidden 384: wide_rollout
+    # table envs (nodes=None): every kernel that draws inside a rollout.  96 lanes leave the last 32-row
+    # tile ragged; a 4-row table ends every episode after 3 steps, so the counter's episode word moves
+    _row(2, None, 256, 96, 6, 256, rows=4, id="table-persistent-2"),             # k_sf_roll
+    _row(8, None, 256, 96, 6, 256, rows=4, id="table-persistent-8"),
+    _row(2, None, 256, 96, 6, 256, rows=4, explore=False, id="table-persistent-2-argmax"),
+    _row(4, None, 256, 96, 6, 256, rows=4, per_step=True, id="table-per-step-4"),  # k_sf_fwd16 + k_sample_step
+    _row(4, None, 256, 96, 6, 256, rows=4, prec="fp32", id="table-fp32-4"),       # k_fwd_head<..., FWD_ROLLOUT>
+    _row(4, None, 256, 96, 6, 256, rows=4, prec="fp32", explore=False, id="table-fp32-4-argmax"),
+    _row(4, None, 384, 136, 6, 256, rows=4, id="table-wide-4"),                   # k_wide_sample
 ])
-def test_rollout_replays_from_its_logits(C, nodes, H, N, T, mb):
+def test_rollout_replays_from_its_logits(C, nodes, H, N, T, mb, rows, prec, per_step, explore):
     """PPO.rollout's buffers are what a twin env gives when fed the rollout's own logits through
-    rlks_sample_categorical + rlks_env_step, bit for bit.  With the rollouts on the fused step this
-    holds by the kernels' own arithmetic.  On the commit before them it held for actions, obs,
-    rewards and dones and failed for logp by 1 ulp in 59 of 136 lanes of a step: the rollouts'
-    separate sampler (k_wide_sample) was built with FMA contraction, which rounds logf's last
-    addition differently."""
+    rlks_sample_categorical + rlks_env_step, bit for bit.  Every rollout kernel draws with the one
+    categorical() / categorical_row() of env_device.h, so this holds by the kernels' own arithmetic, on
+    node-level and table envs alike.  Before the node-level rollouts moved to the fused step it failed
+    for logp by 1 ulp in 59 of 136 lanes of a step, and before the draw was shared the table rows
+    failed the same way on the persistent, fp32 and wide paths (profiles/r15_shared_rows): their
+    samplers were built with FMA contraction, which rounds logf's last addition differently
+    (DESIGN.md §18, §24)."""
     from rlks import VecK8sMultiCloudEnv
     from rlks.env import NodeSpec
     from rlks.ppo import PPO, PPOConfig
     from rlks.tables import synthetic_table
 
     d = _dev()
-    tab = synthetic_table(C, 100, seed=7)
-    spec = NodeSpec(C, nodes, arrival_rate=2.0, depart_prob=0.05, init_occupancy=0.5, reject_penalty=0.1)
+    tab = synthetic_table(C, rows, seed=7)
+    spec = None if nodes is None else NodeSpec(C, nodes, arrival_rate=2.0, depart_prob=0.05, init_occupancy=0.5,
+                                               reject_penalty=0.1)
     cfg = (PPOConfig().framework("torch")
            .training(train_batch_size=N * T, sgd_minibatch_size=mb, num_sgd_iter=1, lr=3e-4,
                      model={"fcnet_hiddens": [H, H]})
            .debugging(seed=5))
-    cfg.num_envs, cfg.table, cfg.nodes = N, tab, spec
+    cfg.num_envs, cfg.table, cfg.nodes, cfg.sgd_precision = N, tab, spec, prec
     algo = PPO(config=cfg, device=d)
-    assert algo.T == T and algo.N == N and algo.precision == ("wide" if H != 256 else "sf16")
-    algo.rollout(explore=True)
+    assert algo.T == T and algo.N == N
+    assert algo.precision == ("wide" if H != 256 else "sf16" if prec == "auto" else prec)
+    if per_step:
+        algo.bufs.global_lanes = SF_ROLL_FUSED_MAX_LANES + 1
+    algo.rollout(explore=explore)
     b = algo.buf
     twin = VecK8sMultiCloudEnv(N, table=tab, seed=5, nodes=spec, device=d)
     assert torch.equal(twin.reset(), b["obs"][0])
     y = _Out(N, 3 * C, d)
     for t in range(T):
-        _two_calls(twin, b["logits"][t].contiguous(), 1, y, 5, 0)
+        _two_calls(twin, b["logits"][t].contiguous(), explore, y, 5, 0)
         for g, e, what in zip((b["actions"][t], b["logp"][t], b["obs"][t + 1], b["rewards"][t], b["dones"][t]),
                               (y.actions, y.logp, y.obs, y.reward, y.done),
                               ("actions", "logp", "obs", "rewards", "dones")):
             np.testing.assert_array_equal(_bits(g), _bits(e), err_msg=f"{what}[{t}]")
+    if rows < T:  # episodes ended inside the rollout
+        assert b["dones"].any() and not b["dones"].all()
+    if not explore:  # argmax: the lowest index of the maximum
+        np.testing.assert_array_equal(b["actions"].cpu().numpy(), b["logits"].cpu().numpy().argmax(2))
