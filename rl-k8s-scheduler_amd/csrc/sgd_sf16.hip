@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "sgd_sf16.h"
+#include "sf_exp.h"
 
 namespace rlks {
 
@@ -108,13 +109,7 @@ __device__ __forceinline__ void split16(const f32x16& v, int o, float s, h8& hi,
   split8v(x, hi, lo);
 }
 
-// exponent e with mx 2^e in [2^14, 2^15); 0 for mx = 0 / non-finite
-__device__ __forceinline__ int sf_exp(float mx) {
-  if (!(mx > 0.f) || !(mx <= 3.4e38f)) return 0;
-  int e;
-  (void)frexpf(mx, &e);
-  return min(max(15 - e, -120), 120);
-}
+// (sf_exp, the exponent e with mx 2^e in [2^14, 2^15), and its bit-pattern form: sf_exp.h)
 __device__ __forceinline__ float pow2(int e) { return ldexpf(1.f, e); }
 
 // 1 - 2 / (exp(2x) + 1): 5 VALU ops (2 transcendental); absolute error ~1e-7, which is what the
@@ -1186,12 +1181,23 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // that stays resident is the tile's dZ2 (eight (hi, lo) fragments: 64 registers, handed over by F1a);
 // the accumulators are two tiles (8 registers) instead of 16.
 // Step kt's W2^T chunk is rows [16 kt, 16 kt + 16) x all 256 columns (hc_dma_kt), read by hc_frag(buf, s, ...).
+// A step is bound by vector issue, not by the MFMA pipe (per wave ~700 issue cycles against 480 of MFMA:
+// DESIGN.md §25), so the epilogue keeps off the vector unit whatever is wave-uniform: the k-tile's wave max
+// goes as far as the rows by DPP on the bit patterns, and the max of the four row leaders, the split exponent
+// and the two powers of two are scalar integer arithmetic (sf_exp.h).  Per step 89 -> 61 VALU instructions,
+// the same bits; c4 -2.5 %, c2 -2.2 % (profiles/r16_f1a_ahead).
 //
 // the dW1 slots of the k-tile-major F1b: [2][W][16 k][16 d] floats behind F1b's first W2^T chunk.  They
 // alias nothing (the chunk buffers, the W1a planes and the Xa images are all live during the loop); two,
 // because k-tile kt - 1 is stored in the step that sums k-tile kt - 2
 template <int W>
 constexpr int f1_kt_slot_bytes() { return 2 * W * 16 * 16 * 4; }
+// dpp<> on a bit pattern, with bound_ctrl set: these controls give every lane a source, so the value is the
+// same, and the move folds into the integer max that takes it (a float max would first canonicalize it)
+template <int CTRL>
+__device__ __forceinline__ unsigned dppz(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
 
 template <int NET, int ND, int W, bool W1_KEPT, int XOFF>
 __device__ __forceinline__ void f1b_kt_body(const SfArgs& g, int grp, int edz, int ex, const DzFrag (&dz)[8]) {
@@ -1220,7 +1226,9 @@ __device__ __forceinline__ void f1b_kt_body(const SfArgs& g, int grp, int edz, i
   h4 xth, xtl;
   xs_frag_t(sX, 0, c, gq, (tile & 1) ? 0x80008000u : 0u, xth, xtl);
   const float k_z1 = sgn * N.sc[1] / pow2(ex) * SF_2LOG2E;
-  const int eu = 2 - ex - edz - (int)N.sc[5];  // u1 = sgn 2^(eu - ez), ez the k-tile's split exponent
+  // u1 = sgn 2^(eu - ez), ez the k-tile's split exponent (wave-uniform, in a scalar register for the steps)
+  const int eu = __builtin_amdgcn_readfirstlane(2 - ex - edz - (int)N.sc[5]);
+  const unsigned sgnb = (tile & 1) ? 0x80000000u : 0u;  // (sgn's sign bit)
   const _Float16* w1b = sW1 + w1_off<KD>(c, gq & (KD / 8 - 1));
   float* slot = sEp + (w * 16 + c) * 16 + 4 * (gq ^ ((c >> 1) & 3));  // (the quad swizzle of f1b_body's slots)
 
@@ -1249,8 +1257,19 @@ __device__ __forceinline__ void f1b_kt_body(const SfArgs& g, int grp, int edz, i
       a[i] *= fmaf(-r, r, r);
       zmx = fmaxf(zmx, fabsf(a[i]));
     }
-    const int ez = sf_exp(wave_max(zmx));  // (an all-zero k-tile: 0)
-    const float sz1 = pow2(ez), u1 = sgn * pow2(eu - ez), u1l = u1 * (1.f / 2048.f);
+    // the wave max as far as the rows by DPP (a maximum is exact in any order); the four row leaders go to
+    // the scalar unit, which finishes the max, the exponent and both powers of two on the bit patterns
+    // (sf_exp.h): none of that takes vector issue, which bounds this loop
+    unsigned zb = __float_as_uint(zmx);  // (zmx >= 0 and no NaN: the patterns order as the values do)
+    zb = max(zb, dppz<0xB1>(zb));
+    zb = max(zb, dppz<0x4E>(zb));
+    zb = max(zb, dppz<0x141>(zb));
+    zb = max(zb, dppz<0x128>(zb));
+    const unsigned m01 = max(__builtin_amdgcn_readlane(zb, 0), __builtin_amdgcn_readlane(zb, 16));
+    const unsigned m23 = max(__builtin_amdgcn_readlane(zb, 32), __builtin_amdgcn_readlane(zb, 48));
+    const int ez = sf_exp_bits(max(m01, m23));  // (an all-zero k-tile: 0)
+    const float sz1 = __uint_as_float(pow2_bits(ez));
+    const float u1 = __uint_as_float(pow2_bits(eu - ez) | sgnb), u1l = u1 * (1.f / 2048.f);
     h4 zh, zl;  // (the lo half carried at 2^11, as in f1b_body)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1348,6 +1367,12 @@ __device__ __forceinline__ void f1b_kt_body(const SfArgs& g, int grp, int edz, i
 // waits for no memory round trip; F1b splits dZ1 with v_fma_mix and flushes dW1 four k-tiles a round.
 // LDS: [phase regions, 64 KB at least][Xa images W x 2 KB][W2^T half-chunk 16 KB].  All of it moves the
 // same bits: the gradient is byte-identical to the kernel without them.
+// Tried on this kernel and left out, both byte-identical, the first slower and the second no faster (DESIGN.md §25,
+// profiles/r16_f1a_ahead):
+// H1 of k-tile t + 1 produced in step (t, 1) of F1a's Z2 loop with the waves of a SIMD in opposite orders (the
+// second H1 pair fits the 128 registers only with the Xa fragment re-read from its image; Z2 k-tiles 1-7
+// 34.3 k -> 35.9 k cycles, c4 +1.7 %), and the chain of F1b's k-tile 0 behind the barrier that ends F1a's
+// epilogue (step 0 2.1 k -> 0.9 k cycles, the hand-over 9.5 k -> 10.7 k: chunk 1's round trip is then exposed).
 template <int A_, int KD, int W>
 constexpr bool f1_w1_kept() {  // F1a's epilogue slots end before the W1a planes (sW1 = 4 H16 halves in)
   return W * (A_ - 1 > 1 ? A_ - 1 : 1) * HID * 4 + W * (A_ + 4) * 4 <= 4 * H16 * 2;
