@@ -21,6 +21,7 @@
 #ifndef RLKS_H
 #define RLKS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rlks_types.h"
@@ -246,6 +247,33 @@ int rlks_mlp_layout(const rlks_mlp_desc* desc, int64_t* offsets12, int64_t* padd
 /* logits_dev[n][A], values_dev[n] = FCNet forward of obs_dev[n][D] (either output may be NULL) */
 int rlks_policy_forward(const rlks_mlp_desc* desc, const float* params_dev, const float* obs_dev,
                         int n, float* logits_dev, float* values_dev, void* stream);
+
+/* ---- serving: one launch from n raw observations to decisions.
+ * one launch: raw obs -> (filter) -> policy MLP -> (mask) -> argmax / Categorical draw -> probs; optionally the value.
+ * Every pointer is one the device can dereference: device memory or rlks_host_alloc'd memory.
+ *   filter_state  NULL, or an rlks_obs_filter state for obs_dim columns: every loaded element goes through
+ *                 rlks_obs_filter_apply's arithmetic first (the same bits)
+ *   mask          NULL, or uint64_t[n], bit a set = action a allowed, with rlks_sample_categorical_masked's
+ *                 rules (a row without a bit among the low A counts as unmasked; masked logits become
+ *                 RLKS_MASKED_LOGIT)
+ *   the draw      row i: rlks_sample_categorical[_masked] on the row's logits with ids {sampler_id, i, call}
+ *                 under key = seed, bit for bit (explore = 0: the argmax, lowest index of the maximum)
+ *   outputs       actions[n] (required); any of logp[n] = log pi(action), logits[n][A] = the row as drawn
+ *                 from, probs[n][A] = its softmax (exact zeros where masked), values[n] may be NULL; the
+ *                 value net runs only when values is given
+ * What is written for row i depends on that row, the parameters, the filter state, its mask word and (when
+ * exploring) seed, call and i alone: not on n nor on the other rows.  No atomics: the same bits on every run.
+ * Scope: hidden 256, 1 <= obs_dim <= 192, 1 <= n_actions <= 64; anything else RLKS_ERR_UNSUPPORTED (use
+ * rlks_policy_forward[_ws] + rlks_sample_categorical).  A null desc, params, obs or actions, n < 0 or a
+ * misaligned pointer (params 16 bytes, floats 4, filter state and mask 8): RLKS_ERR_ARG.  Errors are found
+ * before any HIP call; n == 0 returns RLKS_OK without a launch.  Asynchronous on `stream`, capturable. */
+int rlks_policy_act(const rlks_mlp_desc* desc, const float* params_dev, const double* filter_state /* NULL */,
+                    const float* obs, const uint64_t* mask /* NULL */, int n, int explore,
+                    unsigned long long seed, uint32_t sampler_id, uint32_t call,
+                    int32_t* actions, float* logp, float* logits, float* probs, float* values, void* stream);
+/* device-visible pinned host memory (hipHostMalloc mapped + hipHostGetDevicePointer) for zero-copy staging */
+int rlks_host_alloc(size_t bytes, void** host_ptr, void** dev_ptr);
+int rlks_host_free(void* host_ptr);
 
 /* Rollout buffers, time-major, device pointers */
 typedef struct rlks_rollout_bufs {

@@ -6,14 +6,13 @@
 // has_room() (env_device.h), which k_rule_actions<RLKS_RULE_MYOPIC_WITH_ROOM> evaluates too.  The masked
 // draw follows categorical() (env_device.h) operation for operation on the masked row, so a row without a
 // masked entry gives that function's bits; it differs in its fallback index and in writing the masked row
-// back, so it stays a function of its own.  The file is built without FMA contraction, as env.hip is.
+// back, so it stays a function of its own (categorical_masked(), beside categorical() in env_device.h: the
+// serving kernel, policy_act.hip, draws with it too).  The file is built without FMA contraction, as env.hip is.
 #include <hip/hip_runtime.h>
 
 #include "env_device.h"
 
 namespace rlks {
-
-__device__ __forceinline__ uint64_t low_bits(int A) { return A >= 64 ? ~0ull : (1ull << A) - 1ull; }
 
 // mask(lane): bit c = cluster c can take one more pod; every cluster when none can (nothing to choose
 // between: the rule's fallback) and on a table env.  C <= 64 (the entry points check it).
@@ -24,42 +23,6 @@ __device__ __forceinline__ uint64_t room_mask(const EnvView& v, int lane) {
   for (int c = 0; c < C; ++c)
     if (has_room(v, lane, c)) m |= 1ull << c;
   return m ? m : low_bits(C);
-}
-
-// categorical() over the row l[0..A) after the entries outside `mask` were overwritten with
-// RLKS_MASKED_LOGIT (in place: the caller's buffer holds the masked row afterwards).  A mask without a
-// bit among the low A counts as all of them.  One difference from categorical(): when no cumulative
-// entry exceeds u (f32(u53) rounded to 1.0), the action is the highest unmasked index, not A - 1.
-__device__ __forceinline__ int categorical_masked(float* __restrict__ l, int A, uint64_t mask, bool explore, u32x4 ctr,
-                                                  uint32_t k0, uint32_t k1, float& logp) {
-  mask &= low_bits(A);
-  if (!mask) mask = low_bits(A);
-  float mx = 0.f;
-  int amax = 0;
-  for (int a = 0; a < A; ++a) {
-    float x = l[a];
-    if (!((mask >> a) & 1ull)) {
-      x = RLKS_MASKED_LOGIT;
-      l[a] = x;
-    }
-    if (a == 0 || x > mx) { mx = x; amax = a; }
-  }
-  // (from here on the row is read back as the thread itself left it)
-  float s = 0.f;
-  for (int a = 0; a < A; ++a) s += expf(l[a] - mx);
-  int act = amax;
-  if (explore) {
-    const u32x4 x = philox4x32_10(ctr, k0, k1);
-    const float u = (float)u53(x.x, x.y) * s;
-    float c = 0.f;
-    act = 63 - __clzll((long long)mask);
-    for (int a = 0; a < A; ++a) {
-      c += expf(l[a] - mx);
-      if (u < c) { act = a; break; }
-    }
-  }
-  logp = l[act] - mx - logf(s);
-  return act;
 }
 
 // One thread per lane; used_cpu is cluster-major [C][N] (coalesced), the logits row is C contiguous

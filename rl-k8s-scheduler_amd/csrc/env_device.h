@@ -192,6 +192,46 @@ __device__ __forceinline__ int categorical(const float* __restrict__ l, int A, b
   return act;
 }
 
+__device__ __forceinline__ uint64_t low_bits(int A) { return A >= 64 ? ~0ull : (1ull << A) - 1ull; }
+
+// categorical() over the row l[0..A) after the entries outside `mask` were overwritten with
+// RLKS_MASKED_LOGIT (in place: the caller's buffer holds the masked row afterwards).  A mask without a
+// bit among the low A counts as all of them.  One difference from categorical(): when no cumulative
+// entry exceeds u (f32(u53) rounded to 1.0), the action is the highest unmasked index, not A - 1.
+// Shared by action_mask.hip's kernels and the serving kernel (policy_act.hip).
+__device__ __forceinline__ int categorical_masked(float* __restrict__ l, int A, uint64_t mask, bool explore, u32x4 ctr,
+                                                  uint32_t k0, uint32_t k1, float& logp) {
+#pragma clang fp contract(off)
+  mask &= low_bits(A);
+  if (!mask) mask = low_bits(A);
+  float mx = 0.f;
+  int amax = 0;
+  for (int a = 0; a < A; ++a) {
+    float x = l[a];
+    if (!((mask >> a) & 1ull)) {
+      x = RLKS_MASKED_LOGIT;
+      l[a] = x;
+    }
+    if (a == 0 || x > mx) { mx = x; amax = a; }
+  }
+  // (from here on the row is read back as the thread itself left it)
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) s += __builtin_expf(l[a] - mx);
+  int act = amax;
+  if (explore) {
+    const u32x4 x = philox4x32_10(ctr, k0, k1);
+    const float u = (float)u53(x.x, x.y) * s;
+    float c = 0.f;
+    act = 63 - __clzll((long long)mask);
+    for (int a = 0; a < A; ++a) {
+      c += __builtin_expf(l[a] - mx);
+      if (u < c) { act = a; break; }
+    }
+  }
+  logp = l[act] - mx - __builtin_logf(s);
+  return act;
+}
+
 // categorical() over a row held in registers (A_ known at compile time), for the kernels whose head
 // leaves the logits there: every loop unrolled, each expf(l[a] - mx) taken once and kept, no early
 // exit from the search (a `found` flag), l[act] picked by select so that the row is never indexed

@@ -5,6 +5,14 @@
 
 namespace rlks {
 
+// One filtered element, y = (float)(((double)x - mean[c]) * inv[c]): the apply kernel's arithmetic, and
+// the serving kernel's (policy_act.hip) on the rows it loads, so both give the same bits.  sm / si: the
+// state's mean and inv vectors (global or LDS).  A subtract then a multiply: nothing an FMA could fuse.
+__device__ __forceinline__ float of_one(float x, const double* sm, const double* si, int c, int D) {
+  if (!dcheck((unsigned)c < (unsigned)D, DC_FILTER_COL, c)) c = 0;
+  return (float)(((double)x - sm[c]) * si[c]);
+}
+
 // Optional argument of the rollout host loops (rlks_rollout_filtered): with a tap, the env's
 // observation output of step t goes to raw[t + 1] and one apply launch writes bufs->obs[t + 1] =
 // filter(raw[t + 1]) before the next forward reads it.  Without one (nullptr) the loops issue exactly

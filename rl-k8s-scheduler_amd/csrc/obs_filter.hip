@@ -19,7 +19,7 @@
 // own, as the numpy restatement forms them.
 #include <hip/hip_runtime.h>
 
-#include "rlks_internal.h"
+#include "obs_filter.h"
 
 namespace rlks {
 
@@ -30,11 +30,6 @@ constexpr int OF_PART_MAX_BLOCKS = 1024;   // stats stage one: partial records a
 constexpr int OF_PART_MIN_FLOATS = 16384;  // stats: floats per workgroup before a second one is used
 constexpr int OF_UNROLL = 8;               // stats: loads in flight per thread
 constexpr int OF_FIN_SLOTS = 4, OF_FIN_Q = OF_BLOCK / OF_FIN_SLOTS;
-
-__device__ __forceinline__ float of_one(float x, const double* sm, const double* si, int c, int D) {
-  if (!dcheck((unsigned)c < (unsigned)D, DC_FILTER_COL, c)) c = 0;
-  return (float)(((double)x - sm[c]) * si[c]);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(OF_BLOCK) void k_obs_filter_apply(const double* __restrict__ state, const float* x,

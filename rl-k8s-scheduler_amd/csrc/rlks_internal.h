@@ -55,6 +55,10 @@ enum DcheckSite {
   DC_WIDE_COL = 9,     // wide dZ2 kernel: the thread's 8 columns within H
   DC_FILTER_COL = 10,  // observation filter: the element's column < D
   DC_FILTER_IDX = 11,  // observation filter: the float group / row within the input
+  DC_ACT_ROW = 12,     // serving kernel: a loaded or stored row < n
+  DC_ACT_W2 = 13,      // serving kernel: the last float of a W2 fragment load within [H][H]
+  DC_ACT_LDS = 14,     // serving kernel: an activation / partial / logits slot within its LDS array
+  DC_ACT_HEAD = 15,    // serving kernel: the head's output index < A (1 for the value net)
 };
 #ifdef RLKS_DEBUG
 // every translation unit that includes this header gets its own counters and registers their

@@ -10,6 +10,7 @@ Public surface (mirrors the reference's gymnasium env and RLlib PPO call sites):
     build_reference_table, synthetic_table     rlks.tables (generate_real_pricing.py, normalize_data.py)
     latest_checkpoint, run_experiment          rlks.checkpoints (final_evaluation.py:13-25, train_final.py:22-35)
     JsonLinesReporter                          rlks.metrics (train_ppo.py:29-30 per-iteration report)
+    PolicyServer                               rlks.serving (one-launch decisions from a checkpoint)
 All compute runs in librlks.so (hand-written gfx950 HIP kernels); there is no CPU fallback.
 """
 from .checkpoints import find_checkpoints, latest_checkpoint, results_root, run_experiment  # noqa: F401
@@ -33,6 +34,10 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
         from . import evaluation
 
         return getattr(evaluation, name)
+    if name == "PolicyServer":
+        from .serving import PolicyServer
+
+        return PolicyServer
     if name == "PolicyParams":
         from .policy import PolicyParams
 

@@ -134,6 +134,10 @@ SIGNATURES = {
     "rlks_adv_finalize": [_P, _P, _P],
     "rlks_mlp_layout": [C.POINTER(MlpDesc), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)],
     "rlks_policy_forward": [C.POINTER(MlpDesc), _P, _P, _I, _P, _P, _P],
+    "rlks_policy_act": [C.POINTER(MlpDesc), _P, _P, _P, _P, _I, _I, C.c_ulonglong, C.c_uint32, C.c_uint32, _P, _P, _P,
+                        _P, _P, _P],
+    "rlks_host_alloc": [C.c_size_t, C.POINTER(_P), C.POINTER(_P)],
+    "rlks_host_free": [_P],
     "rlks_rollout": [_P, C.POINTER(MlpDesc), _P, C.POINTER(RolloutBufs), _I, _P],
     "rlks_gemm_sf16": [C.POINTER(GemmDesc), _P],
     "rlks_absmax": [_P, _I, _I, _I, _P, _P],

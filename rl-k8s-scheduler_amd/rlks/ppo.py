@@ -904,6 +904,16 @@ class PPO:
             action_mask = np.asarray(action_mask, dtype=bool).reshape(1, self.A)
         return int(self._sample(logits, explore, action_mask).item())
 
+    def server(self, max_rows=1024):
+        """an rlks.serving.PolicyServer over this algorithm's live parameters and filter state (no copy:
+        after train() it serves the new weights): one launch per act() call instead of
+        compute_single_action's sequence.  Its call counter is its own and starts at 0; it is not
+        sample_calls."""
+        from .serving import PolicyServer
+
+        return PolicyServer(self.params, obs_filter=self.obs_filter, masked=self.action_mask is not None,
+                            seed=self.seed, max_rows=max_rows, device=self.device, explore=self.config.explore)
+
     def current_obs(self):
         """the lanes' current observations [N, D] (device): what the env returned, so raw ones under
         an observation filter (compute_actions(current_obs()) filters them once)"""
