@@ -454,7 +454,7 @@ def _mix32(x):
 
 
 def perm_keys(seed: int, epoch: int, S: int):
-    """(half, mask, round keys) of the per-epoch Feistel bijection (csrc/ppo.hip make_perm)"""
+    """(half, mask, round keys) of the per-epoch Feistel bijection (csrc/gather.hip make_perm)"""
     bits = 2
     while (1 << bits) < S:
         bits += 1
@@ -475,7 +475,7 @@ def perm_keys(seed: int, epoch: int, S: int):
 def epoch_permutation(seed: int, epoch: int, S: int) -> np.ndarray:
     """sample index (t * N + n) of every minibatch row position of epoch `epoch`: a balanced
     4-round Feistel network on [0, 2^(2 half)) cycle-walked into [0, S) — restates
-    csrc/ppo.hip perm_apply / k_gather (rows b*mb .. (b+1)*mb of the result form minibatch b)"""
+    csrc/gather.h perm_apply / gather.hip k_gather (rows b*mb .. (b+1)*mb of the result form minibatch b)"""
     half, mask, keys = perm_keys(seed, epoch, S)
     x = np.arange(S, dtype=np.uint64)
     out = np.empty(S, np.uint64)
@@ -495,7 +495,7 @@ def epoch_permutation(seed: int, epoch: int, S: int) -> np.ndarray:
     return out.astype(np.int64)
 
 
-GROUP_KEY = 0x632BE59BD9B4E019  # csrc/ppo.hip rlks_ppo_gather_grouped: per-group seed offset
+GROUP_KEY = 0x632BE59BD9B4E019  # csrc/gather.hip gather_args: per-group seed offset
 
 
 def minibatch_indices(seed: int, epoch: int, T: int, N: int, mb: int, groups: int = 1, group0: int = 0):

@@ -32,6 +32,20 @@ int fail(int code, const std::string& msg);
 
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// Workspace cursor: hands out consecutive pieces of one allocation, each starting on a 256-byte step.
+// A null base gives null pointers, so the same layout code also just counts bytes (`o` afterwards).
+inline int64_t ws_round(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+struct WsCursor {
+  char* base;
+  int64_t o = 0;
+  template <typename T>
+  T* take(int64_t bytes) {
+    char* p = base ? base + o : nullptr;
+    o += ws_round(bytes);
+    return reinterpret_cast<T*>(p);
+  }
+};
+
 // runtime form switch (common.hip): true only when the environment variable's value starts with '1'
 bool env_on(const char* name);
 

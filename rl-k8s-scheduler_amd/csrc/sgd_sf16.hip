@@ -1705,7 +1705,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_sf_dw2r(SfArgs g) {
 // ----------------------------------------------------------------------------- forward only
 // Rollout forward of both nets on 16-row tiles (the F1a schedule above without the loss and the
 // backward epilogue): logits [M][A] of the policy net and values [M] of the value net for M
-// observation rows of stride D.  The node-level rollout (ppo.hip node_rollout) runs it once per step
+// observation rows of stride D.  The node-level rollout (rollout.hip node_rollout) runs it once per step
 // and for the bootstrap; k_sf_roll's 32-row tiles needed 256 registers per wave (2 waves per SIMD),
 // here a wave holds one 16 x 256 accumulator block and four waves share a SIMD.
 // Rows past M (the last tile of a ragged M) are computed on row M - 1 and not stored.

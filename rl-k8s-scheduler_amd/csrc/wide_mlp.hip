@@ -30,35 +30,30 @@ enum { SL_X = 0, SL_W1, SL_W2, SL_W3, SL_H1, SL_H2, SL_DOUT, SL_DZ2, SL_DZ1, SL_
 
 WideWs wide_ws_layout(int D, int H, int A, int M, char* base) {
   WideWs w{};
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  WsCursor c{base};
   w.M = M;
   const int Mp = (M + 31) / 32 * 32;  // plane rows: the dW2 reduction runs over whole 32-row chunks
   w.blocks = (M + LOSS_ROWS - 1) / LOSS_ROWS;
   for (int net = 0; net < 2; ++net) {
     const int An = net == 0 ? A : 1;
     WideNet& n = w.n[net];
-    n.h1h = (_Float16*)take(2LL * Mp * H);
-    n.h1l = (_Float16*)take(2LL * Mp * H);
-    n.h2 = (float*)take(4LL * M * H);
-    n.w2h = (_Float16*)take(2LL * H * H);
-    n.w2l = (_Float16*)take(2LL * H * H);
-    n.w1h = (_Float16*)take(2LL * H * D);
-    n.w1l = (_Float16*)take(2LL * H * D);
-    n.out = (float*)take(4LL * M * An);
-    n.dout = (float*)take(4LL * M * An);
-    n.slots = (unsigned*)take(4 * SL_N);
-    n.part_stat = (float*)take(4LL * w.blocks * 4);
+    n.h1h = c.take<_Float16>(2LL * Mp * H);
+    n.h1l = c.take<_Float16>(2LL * Mp * H);
+    n.h2 = c.take<float>(4LL * M * H);
+    n.w2h = c.take<_Float16>(2LL * H * H);
+    n.w2l = c.take<_Float16>(2LL * H * H);
+    n.w1h = c.take<_Float16>(2LL * H * D);
+    n.w1l = c.take<_Float16>(2LL * H * D);
+    n.out = c.take<float>(4LL * M * An);
+    n.dout = c.take<float>(4LL * M * An);
+    n.slots = c.take<unsigned>(4 * SL_N);
+    n.part_stat = c.take<float>(4LL * w.blocks * 4);
   }
-  w.dzb = (float*)take(4LL * M * H);
-  w.dzh = (_Float16*)take(2LL * Mp * H);
-  w.dzl = (_Float16*)take(2LL * Mp * H);
-  w.xh = (_Float16*)take(2LL * Mp * D);  // rows [M, Mp) zeroed by wide_grad (dW1's K runs over Mp)
-  w.xl = (_Float16*)take(2LL * Mp * D);
+  w.dzb = c.take<float>(4LL * M * H);
+  w.dzh = c.take<_Float16>(2LL * Mp * H);
+  w.dzl = c.take<_Float16>(2LL * Mp * H);
+  w.xh = c.take<_Float16>(2LL * Mp * D);  // rows [M, Mp) zeroed by wide_grad (dW1's K runs over Mp)
+  w.xl = c.take<_Float16>(2LL * Mp * D);
   {  // weight-gradient partials: dW3 [A][H], dW2 [H][H], dW1 [H][D] (K = M), column sums of M rows
     int64_t pf = (int64_t)2 * colsum_splits(M) * H;  // (hi, lo planes)
     pf = std::max(pf, (int64_t)gemm_splits(A, H, M) * A * H);
@@ -66,10 +61,10 @@ WideWs wide_ws_layout(int D, int H, int A, int M, char* base) {
     pf = std::max(pf, (int64_t)gemm_ps_splits(H, D, Mp) * H * D);
     pf = std::max(pf, (int64_t)gemm_splits(H, D, M) * H * D);
     pf = std::max(pf, (int64_t)2 * ((M + 511) / 512) * H);  // k_wide_dz2's db2 partials (DZ_ROWS x DZ_RT rows each; hi, lo)
-    w.part = (float*)take(4 * pf);
+    w.part = c.take<float>(4 * pf);
   }
-  w.stat_slots = (unsigned*)take(4 * 4);
-  w.bytes = o;
+  w.stat_slots = c.take<unsigned>(4 * 4);
+  w.bytes = c.o;
   return w;
 }
 

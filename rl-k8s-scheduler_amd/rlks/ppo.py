@@ -349,7 +349,7 @@ class PPO:
         groups = int(cfg.num_lane_groups or self.world)
         if (groups % self.world or self.N % (groups // self.world) or self.mb % (groups // self.world)
                 or groups // self.world > 64):
-            # 64 = the gather's lane-group limit (ppo.hip MAX_GROUPS); shares above 8 (NEXT_GROUPS)
+            # 64 = the gather's lane-group limit (gather.h MAX_GROUPS); shares above 8 (NEXT_GROUPS)
             # gather in a launch of their own instead of inside the gradient reduce
             raise ValueError(f"num_lane_groups {groups} must be a multiple of the {self.world} ranks and its per-rank "
                              f"share (at most 64) must divide the {self.N} lanes and the {self.mb}-row minibatch")

@@ -210,7 +210,7 @@ def test_python_sample_step():
         Q.sample_step(torch.zeros(case.n, case.C, device=d))
 
 
-SF_ROLL_FUSED_MAX_LANES = 16384  # (ppo.hip) above it a split-fp16 table rollout runs k_sf_fwd16 + k_sample_step per step
+SF_ROLL_FUSED_MAX_LANES = 16384  # (workspace.h) above it a split-fp16 table rollout runs k_sf_fwd16 + k_sample_step per step
 
 
 def _row(C, nodes, H, N, T, mb, rows=100, prec="auto", per_step=False, explore=True, id=None):

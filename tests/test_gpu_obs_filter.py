@@ -20,7 +20,7 @@ from rollout_metrics_ref import sum_bound
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-# csrc/ppo.hip: above this many lanes the unfiltered split-fp16 table rollout runs the per-step kernels
+# csrc/workspace.h: above this many lanes the unfiltered split-fp16 table rollout runs the per-step kernels
 SF_ROLL_FUSED_MAX_LANES = 16384
 # csrc/obs_filter.hip: columns at most; stats: floats per workgroup, workgroups at most
 OF_MAX_D, OF_PART_MIN_FLOATS, OF_PART_MAX_BLOCKS = 512, 16384, 1024
