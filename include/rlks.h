@@ -567,6 +567,49 @@ int rlks_rollout_filtered(rlks_env* env, const rlks_mlp_desc* desc, const float*
                           const rlks_rollout_bufs* bufs, int explore, void* workspace, int64_t ws_bytes,
                           const double* state_dev, float* raw_dev, void* stream);
 
+/* ============================================================== off-policy evaluation ===== */
+/* What a target policy would have earned on logged decisions (rlks.offline.estimate): RLlib's
+ * ImportanceSampling and WeightedImportanceSampling estimators restated (RLlib is absent from the reference
+ * tree; tests/ope_ref.py pins the arithmetic).  Every entry is asynchronous on `stream`, reads nothing on the
+ * host and is capturable; there are no floating-point atomics, and every addition's place depends on (T, N)
+ * alone: the same buffers give the same bytes on every call.
+ *
+ * rlks_ope_logp: logp_out_dev[i] = log softmax(logits_dev[i])[actions_dev[i]] = l[a] - mx - log(sum exp(l - mx)),
+ * rows i < rows of logits_dev[rows][A] (read only), by the operation sequence of rlks_sample_categorical's
+ * draw, so the logp of an action that draw chose comes back bit for bit.  mask_dev (may be NULL): uint64_t[rows]
+ * with rlks_sample_categorical_masked's rules (entries outside the mask read as RLKS_MASKED_LOGIT, a mask
+ * without a bit among the low A counts as all of them) and that draw's bits; A > 64 with a mask:
+ * RLKS_ERR_UNSUPPORTED.  An action outside [0, A) gives NaN.  rows = 0 launches nothing.
+ *
+ * rlks_ope_estimate: inputs time-major [T][N]: logp_new (target policy), logp_old (behaviour policy, as
+ * logged), rewards (f32) and dones (u8).  In lane n a segment starts at t = 0 and after every non-zero done;
+ * it ends at its done step or at T - 1 (then it is truncated).  Every segment is counted, with
+ * drop_truncated != 0 only those ending in a done; an uncounted segment contributes to nothing.  Per step
+ * k = t - start of a counted segment, every f32 widened to f64 first and every operation rounded on its own:
+ *   lr = logp_new - logp_old;  L_k = L_{k-1} + lr (L_{-1} = 0);  p_k = exp(min(L_k, RLKS_OPE_LMAX));
+ *   g_k = g_{k-1} * gamma (g_0 = 1);  x_k = g_k * r;
+ *   v_behavior = sum_k x_k;  v_is = sum_k p_k x_k   (ascending k, from 0.0);
+ *   S_k = sum of p_k over the counted segments that reach step k, c_k = their number, w_k = S_k / c_k;
+ *   v_wis = sum_k (p_k / w_k) x_k, a term being 0.0 where S_k == 0;  p_end = p at the segment's last step.
+ * record_dev = double[RLKS_OPE_SIZE] (rlks_types.h).  ep_out_dev (may be NULL): double[T][N][4]; at (t_end, n)
+ * of every counted segment {v_behavior, v_is, v_wis, p_end}, untouched elsewhere.  Four launches:
+ *   columns  one thread per lane walks t = 0 .. and adds p_k into its own column of a [T][N] f64 matrix (and 1
+ *            into a u32 one) in program order, noting the rows it reached;
+ *   rows     one workgroup per k: S_k and c_k over n (thread i adds lanes i, i + 256, .. in that order, lanes
+ *            meet by xor butterflies, waves in wave order), then w_k;
+ *   values   the walk again with w_k: the segments' values, ep_out, and per lane the record's sums in segment
+ *            order; a workgroup's lanes meet as above and leave one partial record;
+ *   final    one workgroup adds the partial records (thread i: records i, i + 256, .., then as above).
+ * The workspace is rlks_ope_workspace_bytes(T, N) bytes (12 T N and a little), 8-byte aligned, and holds
+ * nothing between calls.  RLKS_ERR_ARG: a null pointer, T or N < 1, gamma not finite or outside [0, 1], a
+ * misaligned pointer (floats 4 bytes, doubles and the workspace 8), a workspace that is too small. */
+int rlks_ope_logp(const float* logits_dev, const int32_t* actions_dev, const uint64_t* mask_dev /* NULL */,
+                  int64_t rows, int A, float* logp_out_dev, void* stream);
+int rlks_ope_workspace_bytes(int T, int N, int64_t* bytes);
+int rlks_ope_estimate(const float* logp_new_dev, const float* logp_old_dev, const float* rewards_dev,
+                      const uint8_t* dones_dev, int T, int N, double gamma, int drop_truncated, double* record_dev,
+                      double* ep_out_dev /* NULL */, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

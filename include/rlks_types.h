@@ -199,6 +199,29 @@ enum {
   RLKS_OFR_SUMS = 1
 };
 
+/* Off-policy evaluation record written by rlks_ope_estimate (double[RLKS_OPE_SIZE]), over the
+ * counted segments of a decision log: counts are exact integers held in doubles; per segment v_behavior =
+ * sum x_k, v_is = sum p_k x_k, v_wis = sum (p_k / w_k) x_k and p_end = p at its last step, all f64; the *_SUM
+ * slots add them over the segments, the *_SQ slots their squares (formed in f64). */
+enum {
+  RLKS_OPE_EPISODES = 0,  /* counted segments */
+  RLKS_OPE_STEPS = 1,     /* their steps */
+  RLKS_OPE_MAX_LEN = 2,   /* the longest one's steps */
+  RLKS_OPE_CLAMPED = 3,   /* steps with L_k > RLKS_OPE_LMAX */
+  RLKS_OPE_BAD_ROWS = 4,  /* steps whose logp_new or logp_old is not finite: the other slots are then unspecified */
+  RLKS_OPE_VB_SUM = 5,
+  RLKS_OPE_VB_SQ = 6,
+  RLKS_OPE_VIS_SUM = 7,
+  RLKS_OPE_VIS_SQ = 8,
+  RLKS_OPE_VWIS_SUM = 9,
+  RLKS_OPE_VWIS_SQ = 10,
+  RLKS_OPE_PEND_SUM = 11,
+  RLKS_OPE_PEND_SQ = 12,
+  RLKS_OPE_SIZE = 13
+};
+/* the cumulative log ratio L_k enters exp() as min(L_k, RLKS_OPE_LMAX): exp(700) ~ 1.0e304 is finite in f64 */
+#define RLKS_OPE_LMAX 700.0
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,33 @@ __device__ __forceinline__ int categorical_masked(float* __restrict__ l, int A, 
   return act;
 }
 
+// logp of a given action under the row l[0..A): the max, the sum and the last line of categorical(), or,
+// with `masked`, of categorical_masked(), in their order on the same values, so an action one of them drew
+// gets the logp it returned, bit for bit.  The row is only read: a masked entry is formed when it is used
+// (RLKS_MASKED_LOGIT wherever the mask has no bit), never stored.  An action outside [0, A): NaN.
+// (rlks_ope_logp, ope.hip)
+__device__ __forceinline__ float categorical_logp(const float* __restrict__ l, int A, bool masked, uint64_t mask,
+                                                  int act) {
+#pragma clang fp contract(off)
+  if (masked) {
+    mask &= low_bits(A);
+    if (!mask) mask = low_bits(A);
+  }
+  float mx = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float x = (masked && !((mask >> a) & 1ull)) ? RLKS_MASKED_LOGIT : l[a];
+    if (a == 0 || x > mx) mx = x;
+  }
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float x = (masked && !((mask >> a) & 1ull)) ? RLKS_MASKED_LOGIT : l[a];
+    s += __builtin_expf(x - mx);
+  }
+  if ((unsigned)act >= (unsigned)A) return __builtin_nanf("");
+  const float la = (masked && !((mask >> act) & 1ull)) ? RLKS_MASKED_LOGIT : l[act];
+  return la - mx - __builtin_logf(s);
+}
+
 // categorical() over a row held in registers (A_ known at compile time), for the kernels whose head
 // leaves the logits there: every loop unrolled, each expf(l[a] - mx) taken once and kept, no early
 // exit from the search (a `found` flag), l[act] picked by select so that the row is never indexed

@@ -73,6 +73,12 @@ enum DcheckSite {
   DC_ACT_W2 = 13,      // serving kernel: the last float of a W2 fragment load within [H][H]
   DC_ACT_LDS = 14,     // serving kernel: an activation / partial / logits slot within its LDS array
   DC_ACT_HEAD = 15,    // serving kernel: the head's output index < A (1 for the value net)
+  DC_OPE_STEP = 16,    // off-policy estimate: the step read, t N + n < T N
+  DC_OPE_COL = 17,     // off-policy estimate: the column entry, k N + n < T N (k <= t)
+  DC_OPE_ROW = 18,     // off-policy estimate: the row of S_k / w_k, k < T
+  DC_OPE_PART = 19,    // off-policy estimate: a partial record < workgroups
+  DC_OPE_EP = 20,      // off-policy estimate: the per-episode entry, t N + n < T N
+  DC_OPE_LOGIT = 21,   // rlks_ope_logp: the row < rows
 };
 #ifdef RLKS_DEBUG
 // every translation unit that includes this header gets its own counters and registers their

@@ -11,6 +11,8 @@ Public surface (mirrors the reference's gymnasium env and RLlib PPO call sites):
     latest_checkpoint, run_experiment          rlks.checkpoints (final_evaluation.py:13-25, train_final.py:22-35)
     JsonLinesReporter                          rlks.metrics (train_ppo.py:29-30 per-iteration report)
     PolicyServer                               rlks.serving (one-launch decisions from a checkpoint)
+    DecisionLog, estimate                      rlks.offline (off-policy IS / WIS estimates on logged decisions,
+                                                            DESIGN.md §28)
 All compute runs in librlks.so (hand-written gfx950 HIP kernels); there is no CPU fallback.
 """
 from .checkpoints import find_checkpoints, latest_checkpoint, results_root, run_experiment  # noqa: F401
@@ -38,6 +40,10 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
         from .serving import PolicyServer
 
         return PolicyServer
+    if name in ("DecisionLog", "estimate"):
+        from . import offline
+
+        return getattr(offline, name)
     if name == "PolicyParams":
         from .policy import PolicyParams
 

@@ -34,6 +34,11 @@ RLKS_EPLOG_CAP = 128
 # observation-filter state / record layout (include/rlks_types.h RLKS_OF_*, RLKS_OFR_*)
 RLKS_OF_COUNT, RLKS_OF_VECS, RLKS_OF_MEAN, RLKS_OF_M2, RLKS_OF_INV, RLKS_OF_NVEC = 0, 1, 0, 1, 2, 3
 RLKS_OFR_ROWS, RLKS_OFR_SUMS = 0, 1
+# rlks_ope_estimate record slots and the clamp of the cumulative log ratio (include/rlks_types.h RLKS_OPE_*)
+(RLKS_OPE_EPISODES, RLKS_OPE_STEPS, RLKS_OPE_MAX_LEN, RLKS_OPE_CLAMPED, RLKS_OPE_BAD_ROWS, RLKS_OPE_VB_SUM,
+ RLKS_OPE_VB_SQ, RLKS_OPE_VIS_SUM, RLKS_OPE_VIS_SQ, RLKS_OPE_VWIS_SUM, RLKS_OPE_VWIS_SQ, RLKS_OPE_PEND_SUM,
+ RLKS_OPE_PEND_SQ, RLKS_OPE_SIZE) = range(14)
+RLKS_OPE_LMAX = 700.0
 # invalid-action masking (include/rlks_types.h): the sentinel a masked logit is overwritten with, and the
 # threshold at or below which a logit counts as masked
 RLKS_MASKED_LOGIT, RLKS_MASKED_LOGIT_MAX = -1e30, -1e29
@@ -182,6 +187,9 @@ SIGNATURES = {
     "rlks_obs_filter_stats": [_P, _P, _I64, _I, _P, _P, _I64, _P],
     "rlks_obs_filter_merge": [_P, _P, _I, _P],
     "rlks_rollout_filtered": [_P, C.POINTER(MlpDesc), _P, C.POINTER(RolloutBufs), _I, _P, _I64, _P, _P, _P],
+    "rlks_ope_logp": [_P, _P, _P, _I64, _I, _P, _P],
+    "rlks_ope_workspace_bytes": [_I, _I, C.POINTER(_I64)],
+    "rlks_ope_estimate": [_P, _P, _P, _P, _I, _I, C.c_double, _I, _P, _P, _P, _I64, _P],
 }
 _RESTYPES = {"rlks_last_error": C.c_char_p, "rlks_version": C.c_char_p}
 
