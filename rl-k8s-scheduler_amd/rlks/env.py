@@ -31,6 +31,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
+from .sampling import unpack_mask
 from .spaces import Box, Discrete
 from .tables import load_table
 
@@ -492,7 +493,7 @@ class VecK8sMultiCloudEnv:
         torch = _torch()
         bits = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
         _lib.call("rlks_env_action_mask", self.handle, _lib.ptr(bits), self.dev.stream)
-        return ((bits[:, None] >> torch.arange(self.n_clouds, device=self.device)[None, :]) & 1).to(torch.bool)
+        return unpack_mask(bits, self.n_clouds)
 
     def masked_sample(self, logits, explore=True):
         """Categorical sample (explore) or argmax of `logits` [N, C] under the env's action mask, one kernel

@@ -31,6 +31,7 @@ import numpy as np
 
 from . import _lib
 from .env import VecK8sMultiCloudEnv
+from .sampling import mask_on, resolve_policy
 from .tables import load_table
 
 BASELINE_COST = 4.765          # final_evaluation.py:73
@@ -88,20 +89,59 @@ class EvalResult:
                 f"{self.names[0]} choices: {ch[self.names[0]]} | {self.names[1]} choices: {ch[self.names[1]]}\n")
 
 
-def _params_of(policy):
-    """PolicyParams of a PPO algorithm or the params themselves"""
-    return getattr(policy, "params", policy)
+def decider(policy, env, *, explore=False, masked=False, table_rules=False):
+    """The decide step of every loop here and of DecisionLog.collect, built once per run -> (decide, forward):
+    decide(obs, t) -> (actions int32 [N], logp float32 [N] or None) for `env`'s lanes.  `policy`: a
+    sampling.Policy, which decides by forward(obs) (the logits, in scratch owned here; None for a rule) and then
+    their first maximum (np.argmax) or, with `masked`, env.masked_sample(logits, explore=explore); or a rule
+    name, decided on the device by env.rule_actions -- except that with `table_rules` "round_robin" and "greedy"
+    are the reference's two table-env baselines (train_and_compare.py:65, k8s_multi_cloud_env.py:156-157)."""
+    import torch
+
+    N, dev = env.num_envs, env.device
+    if isinstance(policy, str):
+        if table_rules and policy == "round_robin":
+            return (lambda obs, t: (torch.full((N,), t % 2, dtype=torch.int32, device=dev), None)), None
+        if table_rules and policy == "greedy":
+            return (lambda obs, t: ((obs[:, 0] > obs[:, 1]).to(torch.int32), None)), None
+        return (lambda obs, t: (env.rule_actions(policy), None)), None
+    logits = torch.empty(N, env.n_clouds, dtype=torch.float32, device=dev)
+    values = torch.empty(N, dtype=torch.float32, device=dev)
+
+    def forward(obs):
+        if policy.filter is not None:
+            obs = policy.filter.apply(obs)
+        return policy.params.forward(obs, logits, values)[0]
+
+    if masked:
+        return (lambda obs, t: env.masked_sample(forward(obs), explore=explore)), forward
+    return (lambda obs, t: (torch.argmax(forward(obs), dim=1).to(torch.int32), None)), forward
 
 
-def _mask_on(policy, action_mask, nodes):
-    """whether an evaluation decides under the env's action mask: action_mask None = the
-    setting of the PPO algorithm passed as `policy` (off for bare parameters and rules)"""
-    on = getattr(policy, "action_mask", None) is not None if action_mask is None else bool(action_mask)
-    if on and isinstance(policy, str):
-        raise ValueError("action_mask applies to a policy, not to a rule")
-    if on and nodes is None:
-        raise ValueError("action_mask needs a node-level env: a table env has room everywhere")
-    return on
+def run_episodes(env, obs, decide, steps, *, actions=False, util=False, check_done=True):
+    """`steps` steps of a prepared env (seeded and reset by the caller: obs is what reset() returned) under
+    `decide`.  -> (returns float64 [N], summed in step order from 0.0 as `ep_reward += reward` does; the
+    actions int32 [steps, N] or None; the utilisation columns of every step's observation summed, float64
+    [N, C], or None): device tensors.  Raises what check_status raises, and RuntimeError when check_done and
+    a lane has not terminated."""
+    import torch
+
+    N, C_ = env.num_envs, env.n_clouds
+    ret = torch.zeros(N, dtype=torch.float64, device=env.device)
+    acts = torch.empty(steps, N, dtype=torch.int32, device=env.device) if actions else None
+    usum = torch.zeros(N, C_, dtype=torch.float64, device=env.device) if util else None
+    for t in range(steps):
+        a = decide(obs, t)[0]
+        if acts is not None:
+            acts[t] = a
+        obs, r, term, _, _ = env.step(a)
+        ret += r
+        if usum is not None:
+            usum += obs[:, 2 * C_:]
+    env.check_status()
+    if check_done and not bool(term.all()):
+        raise RuntimeError("evaluation lanes did not terminate after max_steps")
+    return ret, acts, usum
 
 
 def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=None,
@@ -123,50 +163,49 @@ def evaluate(policy, num_episodes: int = 100, *, seed=None, table=None, device=N
     if isinstance(policy, str):
         if policy not in ("round_robin", "greedy") and policy not in _lib.RULES:
             raise ValueError(f"unknown baseline policy {policy!r}")
-        params = None
     else:
-        params = _params_of(policy)
-        if params.D != 3 * table.n_clouds or params.A != table.n_clouds:
-            raise ValueError("policy shape does not match the table's clouds")
+        policy = resolve_policy(policy, table)
+        device = policy.params.flat.device if device is None else device
     if seed is None:
         seed = random.getrandbits(64)
     if device is None:
-        device = params.flat.device if params is not None else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device("cuda", torch.cuda.current_device())
     E = int(num_episodes)
     T = table.n_rows - 1  # max_steps (:66): every episode is exactly 99 steps
-    rule = policy if isinstance(policy, str) and policy not in ("round_robin", "greedy") else None
     # (the env's own seed keys only the "random" rule's Philox draws: the MT19937 lanes are seeded below)
     env = VecK8sMultiCloudEnv(E, table=table, noise="mt19937", autoreset=False, device=device,
-                              seed=int(seed) if rule == "random" else 0)
+                              seed=int(seed) if policy == "random" else 0)
     try:
         env.seed([int(seed)] * E)
         per_episode = DRAWS_PER_OBS * (T + 1)
         skip = torch.arange(E, dtype=torch.int64, device=env.device) * per_episode
         _lib.call("rlks_env_mt_discard", env.handle, None, _lib.ptr(skip), env.dev.stream)
-        obs = env.reset()
-        ep_ret = torch.zeros(E, dtype=torch.float64, device=env.device)
-        actions = torch.empty(T, E, dtype=torch.int32, device=env.device)
-        logits = torch.empty(E, table.n_clouds, dtype=torch.float32, device=env.device)
-        values = torch.empty(E, dtype=torch.float32, device=env.device)
-        for t in range(T):
-            if params is not None:
-                params.forward(obs, logits, values)
-                a = torch.argmax(logits, dim=1).to(torch.int32)   # np.argmax: first maximum
-            elif rule is not None:                               # rlks_env_rule_actions, on the device
-                a = env.rule_actions(rule)
-            elif policy == "round_robin":                        # train_and_compare.py:65
-                a = torch.full((E,), t % 2, dtype=torch.int32, device=env.device)
-            else:                                                # normal_scheduler_step (:156-157)
-                a = (obs[:, 0] > obs[:, 1]).to(torch.int32)
-            actions[t] = a
-            obs, r, term, _, _ = env.step(a)
-            ep_ret += r                                          # ep_reward += reward, float64
-        env.check_status()
-        if not bool(term.all()):
-            raise RuntimeError("evaluation lanes did not terminate after max_steps")
-        return EvalResult(ep_ret.cpu().numpy(), actions.cpu().numpy(), baseline_cost,
+        ret, actions, _ = run_episodes(env, env.reset(), decider(policy, env, table_rules=True)[0], T, actions=True)
+        return EvalResult(ret.cpu().numpy(), actions.cpu().numpy(), baseline_cost,
                           CLOUD_NAMES if table.n_clouds == 2 else tuple(f"cluster{c}" for c in range(table.n_clouds)),
                           {"seed": int(seed)})
+    finally:
+        env.close()
+
+
+def _node_run(policy, num_episodes, table, nodes, seed, device, action_mask, full):
+    """the run behind evaluate_nodes (`full`: with the actions, the utilisation sums and the env's counters,
+    which cost atomics and change no result) and evaluate_lanes: lane e of a Philox env keyed by `seed` =
+    episode e, autoreset off, max_steps steps.  -> run_episodes' triple and the counters on the host (or None)"""
+    pol = None
+    if not isinstance(policy, str):
+        policy = pol = resolve_policy(policy, table)
+        if device is None:
+            device = pol.params.flat.device
+    mask = mask_on(pol, action_mask, nodes)
+    env = VecK8sMultiCloudEnv(int(num_episodes), table=table, seed=int(seed), noise="philox", autoreset=False,
+                              device=device, nodes=nodes)
+    try:
+        if full:
+            env.counters(enable=1)
+        out = run_episodes(env, env.reset(), decider(policy, env, masked=mask)[0], env.max_steps, actions=full, util=full,
+                           check_done=full)
+        return (*out, env.counters().cpu().numpy() if full else None)
     finally:
         env.close()
 
@@ -176,34 +215,15 @@ def evaluate_lanes(params, num_episodes: int, *, table=None, nodes=None, seed=0,
     """Greedy (explore=False) float64 returns of `num_episodes` episodes, one lane each, all lanes
     in one batched env: RLlib's evaluation workers (train_final.py:19 .evaluation(
     evaluation_interval=5, evaluation_duration=20), evaluation explore=False).  Table envs run the
-    reference-exact evaluate() above; node-level envs (configs c3 / c5) run Philox lanes keyed by
-    `seed` (episode e = lane e).  action_mask (None = the setting of a PPO algorithm passed as `params`,
-    off otherwise): decide with VecK8sMultiCloudEnv.masked_sample(logits, explore=False), the argmax over
-    the clusters with room."""
-    import torch
-
+    reference-exact evaluate() above; node-level envs (configs c3 / c5) run evaluate_nodes' loop without its
+    counters, so the returns are evaluate_nodes(...).rewards.  action_mask (None = the setting of a PPO
+    algorithm passed as `params`, off otherwise): decide with VecK8sMultiCloudEnv.masked_sample(logits,
+    explore=False), the argmax over the clusters with room."""
     table = table if table is not None else load_table()
-    mask = _mask_on(params, action_mask, nodes)
-    params = _params_of(params)
     if nodes is None:
+        mask_on(resolve_policy(params), action_mask, None)  # asking for a mask here is an error
         return evaluate(params, num_episodes, seed=seed, table=table, device=device).rewards
-    E = int(num_episodes)
-    env = VecK8sMultiCloudEnv(E, table=table, seed=int(seed), noise="philox", autoreset=False, device=device,
-                              nodes=nodes)
-    try:
-        obs = env.reset()
-        ret = torch.zeros(E, dtype=torch.float64, device=env.device)
-        logits = torch.empty(E, table.n_clouds, dtype=torch.float32, device=env.device)
-        values = torch.empty(E, dtype=torch.float32, device=env.device)
-        for _ in range(table.n_rows - 1):
-            params.forward(obs, logits, values)
-            a = env.masked_sample(logits, explore=False)[0] if mask else torch.argmax(logits, dim=1).to(torch.int32)
-            obs, r, term, _, _ = env.step(a)
-            ret += r
-        env.check_status()
-        return ret.cpu().numpy()
-    finally:
-        env.close()
+    return _node_run(params, num_episodes, table, nodes, seed, device, action_mask, False)[0].cpu().numpy()
 
 
 @dataclass
@@ -241,59 +261,18 @@ def evaluate_nodes(policy, num_episodes: int, *, nodes, table=None, seed=0, devi
     was decided, so two calls with the same `seed` and episode count see the same arrival counts at
     every step (placed + rejected is the same), and the same initial occupancy; only placements, and
     with them the departures, differ."""
-    import torch
-
     if num_episodes <= 0:
         raise ValueError("num_episodes must be positive")
     if nodes is None:
         raise ValueError("evaluate_nodes needs a NodeSpec; table envs are evaluate()'s")
     table = table if table is not None else load_table()
-    C_ = table.n_clouds
-    mask = _mask_on(policy, action_mask, nodes)
-    if isinstance(policy, str):
-        if policy not in _lib.RULES:
-            raise ValueError(f"unknown baseline policy {policy!r}; one of {sorted(_lib.RULES)}")
-        params = None
-    else:
-        params = _params_of(policy)
-        if params.D != 3 * C_ or params.A != C_:
-            raise ValueError("policy shape does not match the table's clouds")
-        if device is None:
-            device = params.flat.device
-    E = int(num_episodes)
-    env = VecK8sMultiCloudEnv(E, table=table, seed=int(seed), noise="philox", autoreset=False, device=device,
-                              nodes=nodes)
-    try:
-        T = env.max_steps
-        env.counters(enable=1)
-        obs = env.reset()
-        ret = torch.zeros(E, dtype=torch.float64, device=env.device)
-        util = torch.zeros(E, C_, dtype=torch.float64, device=env.device)
-        actions = torch.empty(T, E, dtype=torch.int32, device=env.device)
-        if params is not None:
-            logits = torch.empty(E, C_, dtype=torch.float32, device=env.device)
-            values = torch.empty(E, dtype=torch.float32, device=env.device)
-        for t in range(T):
-            if params is not None:
-                params.forward(obs, logits, values)
-                a = env.masked_sample(logits, explore=False)[0] if mask else torch.argmax(logits, dim=1).to(torch.int32)
-            else:
-                a = env.rule_actions(policy)
-            actions[t] = a
-            obs, r, term, _, _ = env.step(a)
-            ret += r
-            util += obs[:, 2 * C_:]
-        counters = env.counters()
-        env.check_status()
-        if not bool(term.all()):
-            raise RuntimeError("evaluation lanes did not terminate after max_steps")
-        acts = actions.cpu().numpy()
-        k = counters.cpu().numpy()
-        return NodeEvalResult(ret.cpu().numpy(), acts, np.bincount(acts.reshape(-1), minlength=C_).astype(np.int64),
-                              int(k[1]), int(k[2]), int(k[3]), util.sum(0).cpu().numpy() / (T * E),
-                              {"seed": int(seed)})
-    finally:
-        env.close()
+    if isinstance(policy, str) and policy not in _lib.RULES:
+        raise ValueError(f"unknown baseline policy {policy!r}; one of {sorted(_lib.RULES)}")
+    ret, actions, util, k = _node_run(policy, num_episodes, table, nodes, seed, device, action_mask, True)
+    acts = actions.cpu().numpy()
+    T, E = acts.shape
+    return NodeEvalResult(ret.cpu().numpy(), acts, np.bincount(acts.reshape(-1), minlength=table.n_clouds).astype(np.int64),
+                          int(k[1]), int(k[2]), int(k[3]), util.sum(0).cpu().numpy() / (T * E), {"seed": int(seed)})
 
 
 def comparison_report(results: dict, baseline: str | None = None) -> str:

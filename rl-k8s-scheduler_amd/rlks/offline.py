@@ -29,6 +29,7 @@ from . import _lib
 from ._lib import (RLKS_OPE_BAD_ROWS, RLKS_OPE_CLAMPED, RLKS_OPE_EPISODES, RLKS_OPE_MAX_LEN, RLKS_OPE_PEND_SQ,
                    RLKS_OPE_PEND_SUM, RLKS_OPE_SIZE, RLKS_OPE_STEPS, RLKS_OPE_VB_SQ, RLKS_OPE_VB_SUM, RLKS_OPE_VIS_SQ,
                    RLKS_OPE_VIS_SUM, RLKS_OPE_VWIS_SQ, RLKS_OPE_VWIS_SUM)
+from .sampling import check_mask_width, mask_on, pack_mask, pack_mask_device, resolve_policy
 
 METHODS = {"is": (RLKS_OPE_VIS_SUM, RLKS_OPE_VIS_SQ), "wis": (RLKS_OPE_VWIS_SUM, RLKS_OPE_VWIS_SQ)}
 FORWARD_CHUNK = 1 << 20  # rows per target forward: bounds the logits buffer
@@ -106,18 +107,13 @@ class DecisionLog:
             if m.ndim != 3 or tuple(m.shape[:2]) != (T, N):
                 raise ValueError(f"a bool action_mask must be [{T}, {N}, A], got {list(m.shape)}")
             A = int(m.shape[2])
-            if A > 64:
-                raise ValueError(f"action_mask supports at most 64 actions, got {A}")
+            check_mask_width(A)
             if self.n_actions not in (None, A):
                 raise ValueError(f"action_mask has {A} actions, n_actions says {self.n_actions}")
             self.n_actions = A
             if _is_tensor(m):
-                import torch
-
-                w = torch.ones(A, dtype=torch.int64, device=m.device) << torch.arange(A, device=m.device)
-                return (m.to(torch.int64) * w).sum(2).contiguous()  # bit 63 through the int64's sign bit
-            sh = np.arange(A, dtype=np.uint64)
-            return np.bitwise_or.reduce(np.left_shift(m.astype(np.uint64), sh[None, None, :]), axis=2, dtype=np.uint64)
+                return pack_mask_device(m)
+            return pack_mask(m.reshape(T * N, A), T * N, A).reshape(T, N)
         if name not in ("uint64", "int64") or tuple(m.shape) != (T, N):
             raise ValueError(f"action_mask must be bool [{T}, {N}, A] or 64-bit words [{T}, {N}], got {name} "
                              f"{list(m.shape)}")
@@ -168,22 +164,18 @@ class DecisionLog:
         import torch
 
         from .env import VecK8sMultiCloudEnv
-        from .evaluation import _params_of
+        from .evaluation import decider
         from .tables import load_table
 
         steps, lanes = int(steps), int(lanes)
         if steps < 1 or lanes < 1:
             raise ValueError("collect: steps and lanes must be positive")
         table = table if table is not None else load_table()
-        params = _params_of(policy)
-        masked = getattr(policy, "action_mask", None) is not None
-        if masked and nodes is None:
-            raise ValueError("collect: a policy with action_mask needs a node-level env (nodes=NodeSpec(...))")
+        pol = resolve_policy(policy, table)
+        masked = mask_on(pol, None, nodes)
         A = table.n_clouds
-        if params.D != 3 * A or params.A != A:
-            raise ValueError("policy shape does not match the table's clouds")
         env = VecK8sMultiCloudEnv(lanes, table=table, seed=int(seed), noise="philox", autoreset=True, nodes=nodes,
-                                  device=params.flat.device)
+                                  device=pol.params.flat.device)
         try:
             dev = env.device
             f32 = dict(dtype=torch.float32, device=dev)
@@ -192,44 +184,24 @@ class DecisionLog:
             logp_l, rew_l = torch.empty(steps, lanes, **f32), torch.empty(steps, lanes, **f32)
             done_l = torch.empty(steps, lanes, dtype=torch.uint8, device=dev)
             mask_l = torch.empty(steps, lanes, dtype=torch.int64, device=dev) if masked else None
-            logits, values = torch.empty(lanes, A, **f32), torch.empty(lanes, **f32)
+            decide, forward = decider(pol, env, explore=explore, masked=masked)
             obs = env.reset()
             for t in range(steps):
                 obs_l[t].copy_(obs)
-                params.forward(obs, logits, values)
                 if masked:
                     _lib.call("rlks_env_action_mask", env.handle, _lib.ptr(mask_l[t]), env.dev.stream)
-                    a, lp = env.masked_sample(logits, explore=explore)
-                    act_l[t].copy_(a)
-                    logp_l[t].copy_(lp)
-                    obs, r, done, _, _ = env.step(a)
-                    rew_l[t].copy_(r)  # f64 -> f32, as the rollout stores it
-                else:
-                    a, lp, obs, r, done = env.sample_step(logits, explore=explore)
-                    act_l[t].copy_(a)
-                    logp_l[t].copy_(lp)
-                    rew_l[t].copy_(r)
+                    a, lp = decide(obs, t)
+                    obs, r, done, _, _ = env.step(a)  # r: f64 -> f32 below, as the rollout stores it
+                else:  # the draw and the step in one launch
+                    a, lp, obs, r, done = env.sample_step(forward(obs), explore=explore)
+                act_l[t].copy_(a)
+                logp_l[t].copy_(lp)
+                rew_l[t].copy_(r)
                 done_l[t].copy_(done)
             env.check_status()
             return cls(obs_l, act_l, logp_l, rew_l, done_l, action_mask=mask_l, n_actions=A)
         finally:
             env.close()
-
-
-def _resolve(policy):
-    """-> (PolicyParams, filter to apply before forward or None, masked, whatever must stay alive)"""
-    from .serving import PolicyServer
-
-    if isinstance(policy, (str, Path)):
-        policy = PolicyServer.from_checkpoint(policy)
-    if isinstance(policy, PolicyServer):
-        p = policy.params
-        extra = policy.obs_filter if (policy.obs_filter is not None and p.obs_filter is None) else None
-        return p, extra, policy.masked, policy
-    params = getattr(policy, "params", policy)
-    if not hasattr(params, "forward") or not hasattr(params, "flat"):
-        raise ValueError("policy must be a PPO, a PolicyServer, a PolicyParams or a checkpoint path")
-    return params, None, getattr(policy, "action_mask", None) is not None, policy
 
 
 def _on(x, dev, dtype):
@@ -244,7 +216,11 @@ def target_logp(policy, log):
     for a masked policy.  Forwards in row chunks of at most FORWARD_CHUNK rows, then rlks_ope_logp."""
     import torch
 
-    params, extra, masked, _keep = _resolve(policy)
+    if isinstance(policy, (str, Path)):  # a checkpoint written by PPO.save()
+        from .serving import PolicyServer
+
+        policy = PolicyServer.from_checkpoint(policy)
+    params, extra, masked, _keep = resolve_policy(policy)
     if not isinstance(log, DecisionLog):
         raise ValueError("log must be a DecisionLog")
     if masked and log.action_mask is None:

@@ -45,6 +45,7 @@ import numpy as np
 
 from . import _lib
 from . import distributed as ddp
+from . import sampling
 from .env import DeviceEnv, make_cfg
 from .obs_filter import ObsFilter, validate_observation_filter
 from .policy import PolicyParams
@@ -769,9 +770,8 @@ class PPO:
 
         n = int(episodes or self.config.evaluation_duration)
         seed = (self.seed * 7919 + self.iteration) & 0xFFFFFFFF
-        mask = (self.action_mask is not None) if action_mask is None else bool(action_mask)
-        rets = evaluate_lanes(self.params, n, table=self.table, nodes=self.config.nodes, seed=seed, device=self.device,
-                              action_mask=mask)
+        rets = evaluate_lanes(self, n, table=self.table, nodes=self.config.nodes, seed=seed, device=self.device,
+                              action_mask=action_mask)
         out = {"episode_reward_mean": float(np.mean(rets)), "episode_reward_min": float(np.min(rets)),
                "episode_reward_max": float(np.max(rets)), "episodes_this_iter": n,
                "episode_len_mean": float(self.table.n_rows - 1)}
@@ -837,50 +837,28 @@ class PPO:
             self.reporter.report(result, self)
         return result
 
-    # Philox counter word 0 of policy-side draws (compute_actions / compute_single_action): no env
-    # lane has this id, so these draws never repeat a rollout draw under the same key (config.seed)
-    SAMPLER_ID = 0xFFFFFFFF
+    SAMPLER_ID = sampling.SAMPLER_ID
 
     def _sample(self, logits, explore, action_mask=None):
-        """TorchCategorical sample (explore) or argmax of logits [n, A] on the device sampler
-        (rlks_sample_categorical): row i draws Philox({SAMPLER_ID, i, call counter, ACTION},
-        key = config.seed), so a run's exploring actions follow from the seed and the number of
-        earlier calls (the counter is checkpointed).  action_mask: bool [n, A], True = allowed
-        (rlks_sample_categorical_masked; a row without a True counts as all True); an algorithm
-        configured with action_mask="room" must be given one"""
-        torch = self.torch
+        """sampling.sample_rows on logits [n, A] under config.seed and the call counter sample_calls, so a
+        run's exploring actions follow from the seed and the number of earlier calls (the counter is
+        checkpointed).  action_mask: bool [n, A], True = allowed (a row without a True counts as all True);
+        an algorithm configured with action_mask="room" must be given one"""
         n = logits.shape[0]
         bits = None
         if action_mask is not None:
-            if self.A > 64:
-                raise ValueError(f"action_mask supports at most 64 actions, got {self.A}")
-            m = torch.as_tensor(action_mask, device=self.device).to(torch.bool).reshape(-1, self.A)
+            m = self.torch.as_tensor(action_mask, device=self.device).to(self.torch.bool).reshape(-1, self.A)
             if m.shape[0] != n:
                 raise ValueError(f"action_mask must be [{n}, {self.A}], got {list(m.shape)}")
-            # bit a of row i = m[i, a]; bit 63 through the sign bit of the int64
-            w = torch.ones(self.A, dtype=torch.int64, device=self.device) << torch.arange(self.A, device=self.device)
-            bits = (m.to(torch.int64) * w[None, :]).sum(1).contiguous()
+            bits = sampling.pack_mask_device(m)
         elif self.action_mask is not None:
             raise ValueError("this algorithm was trained with action_mask='room': pass action_mask (bool [n, A], "
                              "e.g. VecK8sMultiCloudEnv.action_mask()); a masked policy acting unmasked would be a "
                              "silent error")
-        logits = logits.contiguous()
-        act = torch.empty(n, dtype=torch.int32, device=self.device)
-        ids = None
+        act, _ = sampling.sample_rows(logits, seed=self.seed, call=self.sample_calls, explore=explore, bits=bits,
+                                      stream=self.stream)
         if explore:
-            idh = np.zeros((n, 3), np.uint32)
-            idh[:, 0] = self.SAMPLER_ID
-            idh[:, 1] = np.arange(n, dtype=np.uint32)
-            idh[:, 2] = self.sample_calls & 0xFFFFFFFF
-            ids = torch.from_numpy(idh.view(np.int32)).to(self.device)
             self.sample_calls += 1
-        if bits is not None:
-            _lib.call("rlks_sample_categorical_masked", _lib.ptr(logits), _lib.ptr(bits), n, logits.shape[1],
-                      _lib.ptr(ids) if ids is not None else None, self.seed & 0xFFFFFFFFFFFFFFFF, int(bool(explore)),
-                      _lib.ptr(act), None, self.stream)
-            return act
-        _lib.call("rlks_sample_categorical", _lib.ptr(logits), n, logits.shape[1], _lib.ptr(ids) if ids is not None else None,
-                  self.seed & 0xFFFFFFFFFFFFFFFF, int(bool(explore)), _lib.ptr(act), None, self.stream)
         return act
 
     def compute_actions(self, obs, explore=None, action_mask=None):
@@ -911,8 +889,9 @@ class PPO:
         sample_calls."""
         from .serving import PolicyServer
 
-        return PolicyServer(self.params, obs_filter=self.obs_filter, masked=self.action_mask is not None,
-                            seed=self.seed, max_rows=max_rows, device=self.device, explore=self.config.explore)
+        pol = sampling.resolve_policy(self)
+        return PolicyServer(pol.params, obs_filter=pol.params.obs_filter, masked=pol.masked, seed=self.seed,
+                            max_rows=max_rows, device=self.device, explore=self.config.explore)
 
     def current_obs(self):
         """the lanes' current observations [N, D] (device): what the env returned, so raw ones under

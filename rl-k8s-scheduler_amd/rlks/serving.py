@@ -12,9 +12,9 @@ the results out of the block: no torch op, no allocation and no explicit copy on
     actions, info = server.act(batch, full_fetch=True) # [n, D] -> int32 [n], RLlib's extra-fetch names
 
 The draw is the shared one: row i of the server's k-th exploring call draws
-Philox({SAMPLER_ID, i, k, ACTION}, key = seed), ``PPO._sample``'s scheme with the server's own counter.
-A policy outside the kernel's scope (hidden != 256, obs_dim > 192, more than 64 actions) is served by
-today's sequence, ``params.forward`` + ``rlks_sample_categorical[_masked]``: ``server.fused`` is False.
+Philox({SAMPLER_ID, i, k, ACTION}, key = seed), the scheme of ``rlks.sampling.sample_rows`` (which
+``PPO.compute_actions`` calls with its own counter).  A policy outside the kernel's scope (hidden != 256,
+obs_dim > 192, more than 64 actions) is served by ``params.forward`` + ``sample_rows``: ``server.fused`` is False.
 """
 from __future__ import annotations
 
@@ -25,27 +25,13 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-
-SAMPLER_ID = 0xFFFFFFFF  # PPO.SAMPLER_ID: counter word 0 of policy-side draws
-
-
-def pack_mask(mask, n, A):
-    """bool [A] or [n, A] (True = allowed) -> uint64 [n], bit a of row i = mask[i, a]"""
-    if A > 64:
-        raise ValueError(f"action_mask supports at most 64 actions, got {A}")
-    m = np.asarray(mask, dtype=bool)
-    if m.shape == (A,):
-        m = np.broadcast_to(m, (n, A))
-    if m.shape != (n, A):
-        raise ValueError(f"action_mask must be [{A}] or [{n}, {A}], got {list(m.shape)}")
-    return np.bitwise_or.reduce(np.left_shift(m.astype(np.uint64), np.arange(A, dtype=np.uint64)[None, :]), axis=1,
-                                dtype=np.uint64)
+from .sampling import SAMPLER_ID, pack_mask, sample_rows  # (SAMPLER_ID and pack_mask: public names of this module too)
 
 
 def check_inputs(D, A, max_rows, masked, obs, action_mask=None):
     """-> (obs float32 [n, D], mask words uint64 [n] or None, single).  ValueError for a wrong D, more
     rows than the staging block holds, a wrong mask shape, or a masked policy asked to act unmasked
-    (the rule of PPO._sample: a masked policy acting unmasked would be a silent error).  Host only."""
+    (the rule of PPO.compute_actions: a masked policy acting unmasked would be a silent error).  Host only."""
     if hasattr(obs, "detach"):
         obs = obs.detach().cpu().numpy()
     x = np.asarray(obs, dtype=np.float32)
@@ -232,34 +218,17 @@ class PolicyServer:
                       "action_prob": self._probs[:n].copy(), "vf_preds": self._values[:n].copy()}
 
     def _act_unfused(self, x, bits, explore, full_fetch):
-        """outside the kernel's scope: compute_actions' sequence, params.forward then
-        rlks_sample_categorical[_masked] with ids {SAMPLER_ID, i, call}"""
+        """outside the kernel's scope: compute_actions' sequence, params.forward then sampling.sample_rows"""
         torch = self._torch
-        n = x.shape[0]
         with torch.cuda.device(self.device):
             o = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
             if self.obs_filter is not None and self.params.obs_filter is None:
                 o = self.obs_filter.apply(o)
             logits, values = self.params.forward(o)
-            logits = logits.contiguous()
-            act = torch.empty(n, dtype=torch.int32, device=self.device)
-            logp = torch.empty(n, dtype=torch.float32, device=self.device)
-            ids = None
+            act, logp = sample_rows(logits, seed=self.seed, call=self.calls, explore=explore, bits=bits,
+                                    want_logp=True, stream=torch.cuda.current_stream(self.device).cuda_stream)
             if explore:
-                idh = np.zeros((n, 3), np.uint32)
-                idh[:, 0] = SAMPLER_ID
-                idh[:, 1] = np.arange(n, dtype=np.uint32)
-                idh[:, 2] = self.calls & 0xFFFFFFFF
-                ids = torch.from_numpy(idh.view(np.int32)).to(self.device)
                 self.calls += 1
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if bits is not None:
-                m = torch.from_numpy(bits.view(np.int64).copy()).to(self.device)
-                _lib.call("rlks_sample_categorical_masked", _lib.ptr(logits), _lib.ptr(m), n, self.A, _lib.ptr(ids),
-                          self.seed, int(explore), _lib.ptr(act), _lib.ptr(logp), stream)
-            else:
-                _lib.call("rlks_sample_categorical", _lib.ptr(logits), n, self.A, _lib.ptr(ids), self.seed,
-                          int(explore), _lib.ptr(act), _lib.ptr(logp), stream)
             acts = act.cpu().numpy()
             if not full_fetch:
                 return acts, None

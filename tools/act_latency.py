@@ -6,6 +6,8 @@
 
 --side server   PolicyServer.act (PPO.server())
 --side algo     PPO.compute_single_action at n = 1, PPO.compute_actions(...).cpu().numpy() at n > 1
+--hidden        the hidden width (default: the config's 256); 128 is outside the act kernel's scope, so that
+                --side server then times the fallback
 --pkg           the package directory to import rlks from (default: this tree's), so that another
                 checkout's build is timed by the same script on the same box
 Grid: n in {1, 16, 256, 1024} x explore in {False, True} x {plain, filter + mask} at (D, A) = (6, 2) and
@@ -28,7 +30,7 @@ SHAPES = ((6, 2), (24, 8))
 WARMUP, CALLS = 200, 2000
 
 
-def build(C_, variant, dev):
+def build(C_, variant, dev, hidden=None):
     from rlks.env import NodeSpec
     from rlks.ppo import PPO, PPOConfig
     from rlks.tables import load_table, synthetic_table
@@ -37,6 +39,8 @@ def build(C_, variant, dev):
            .training(train_batch_size=256 * 8, sgd_minibatch_size=1024, num_sgd_iter=1, lr=3e-4)
            .debugging(seed=11))
     cfg.num_envs, cfg.rollout_fragment_length = 256, 8
+    if hidden:
+        cfg.training(model={"fcnet_hiddens": [hidden, hidden]})
     cfg.table = load_table() if C_ == 2 else synthetic_table(C_, 100, seed=7)
     if variant == "filter+mask":
         cfg.nodes = NodeSpec(C_, 16)
@@ -62,6 +66,8 @@ def main():
     ap.add_argument("--pkg", default=str(ROOT / "rl-k8s-scheduler_amd"))
     ap.add_argument("--out", required=True)
     ap.add_argument("--calls", type=int, default=CALLS)
+    ap.add_argument("--hidden", type=int, default=None, help="e.g. 128: outside rlks_policy_act's scope, so that "
+                    "--side server times the fallback (forward + rlks.sampling.sample_rows)")
     args = ap.parse_args()
     sys.path.insert(0, args.pkg)
     import torch
@@ -70,7 +76,7 @@ def main():
     rows = []
     for D, A in SHAPES:
         for variant in ("plain", "filter+mask"):
-            algo = build(A, variant, dev)
+            algo = build(A, variant, dev, args.hidden)
             assert (algo.D, algo.A) == (D, A)
             obs = np.random.default_rng(5).random((max(NS), D)).astype(np.float32)
             mask = None
@@ -99,7 +105,8 @@ def main():
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"side": args.side, "pkg": args.pkg, "warmup": WARMUP, "calls": args.calls,
-                               "fused": bool(srv.fused) if srv is not None else None, "rows": rows}, indent=1))
+                               "hidden": args.hidden, "fused": bool(srv.fused) if srv is not None else None,
+                               "rows": rows}, indent=1))
 
 
 if __name__ == "__main__":

@@ -20,7 +20,14 @@ gather:  the minibatches of rlks_ppo_pack + rlks_ppo_gather_packed and of rlks_p
          N = 128, 256 rows, two epochs, 1 / 2 / 16 lane groups; 2, 4, 8 actions and the wide record)
 step:    two consecutive SGD steps (the second with prev_fused = 1) through each step entry at 4 actions:
          parameters, Adam moments, gradient, stats and the next minibatch the first step gathered (1 lane
-         group: inside the reduce's launch on sf16; 16: a launch of its own), then rlks_grad_global_norm"""
+         group: inside the reduce's launch on sf16; 16: a launch of its own), then rlks_grad_global_norm
+decide:  what the Python decide paths return, through public entries only: compute_actions and
+         compute_single_action (with the call counters), the server's fallback with full_fetch, evaluate,
+         evaluate_nodes, evaluate_lanes, PPO.evaluate() with baselines, DecisionLog.collect and the estimate with
+         the target passed as a PPO, a PolicyParams, a PolicyServer and a checkpoint.  Here the library is the same
+         and the Python differs: copy this file into a checkout of the other commit and run it there too.
+
+  python tools/refactor_digest.py --decide <out.json>      the decide group alone"""
 import ctypes as C
 import hashlib
 import json
@@ -277,6 +284,145 @@ STEPS = [("sf16", e, g) for e in ("sgd_step_next", "sgd_step_clip", "grad_step_n
 STEPS += [(path, e, 1) for path in ("fp32", "wide") for e in ("sgd_step_next", "sgd_step_clip")]
 
 
+# ---------------------------------------------------------------------------- decide
+def decide_algo(torch, table, nodes=None, H=256, **attrs):
+    from rlks.ppo import PPO, PPOConfig
+
+    cfg = (PPOConfig().framework("torch")
+           .training(train_batch_size=64 * 4, sgd_minibatch_size=256, num_sgd_iter=1, lr=3e-4,
+                     model={"fcnet_hiddens": [H, H]})
+           .debugging(seed=5))
+    cfg.num_envs, cfg.table, cfg.nodes = 64, table, nodes
+    for k, v in attrs.items():
+        setattr(cfg, k, v)
+    return PPO(config=cfg, device=torch.device("cuda", 0))
+
+
+def decide_masks(A, n, seed):
+    """bool [n, A]: random rows, row 0 without an allowed action, row 1 (n > 1) only the top bit (bit 63 at A = 64)"""
+    m = np.random.default_rng(seed).random((n, A)) < 0.5
+    m[0] = False
+    if n > 1:
+        m[1] = False
+        m[1, A - 1] = True
+    return m
+
+
+def decide_digest(torch, tmp):
+    """what the Python decide paths return (rlks.sampling, rlks.evaluation, rlks.offline), public entries only,
+    so that the same file runs on a checkout from before the fold"""
+    import dataclasses
+    import warnings
+
+    import rule_ref as rr
+    from rlks.evaluation import evaluate, evaluate_lanes, evaluate_nodes
+    from rlks.offline import DecisionLog, estimate, run_estimate, target_logp
+    from rlks.policy import PolicyParams
+    from rlks.tables import load_table, synthetic_table
+
+    warnings.simplefilter("ignore", RuntimeWarning)  # save() of a node-level algorithm: env lanes are not kept
+    dev = torch.device("cuda", 0)
+    case = rr.CASES["J"]  # 3 clusters of 8 nodes that fill up (tests/test_action_mask_host.py::test_mask_cases_fill_up)
+    jtab, jspec = synthetic_table(case.C, 100, seed=7), rr.node_spec(case)
+    res = {}
+    # compute_actions / compute_single_action
+    algos = {"table-2": (decide_algo(torch, load_table()), False),
+             "node-masked-8": (decide_algo(torch, synthetic_table(8, 100, seed=7), rr.node_spec(
+                 dataclasses.replace(case, C=8, cpu=(300,) * 8, mem=(4096,) * 8)), action_mask="room"), True),
+             "table-64-with-masks": (decide_algo(torch, synthetic_table(64, 8, seed=7)), True)}
+    for name, (algo, with_mask) in algos.items():
+        r = {"sample_calls": [algo.sample_calls]}
+        obs = np.random.default_rng(5).random((300, algo.D)).astype(np.float32)
+        for n in (300, 1):
+            m = decide_masks(algo.A, n, 3) if with_mask else None
+            for k, explore in enumerate((True, True, True, False)):
+                r[f"n{n}-call{k}"] = sha(algo.compute_actions(obs[:n], explore=explore, action_mask=m))
+                r["sample_calls"].append(algo.sample_calls)
+        for row in (0, 1):
+            m = decide_masks(algo.A, 2, 3)[row] if with_mask else None
+            r[f"single-row{row}"] = [algo.compute_single_action(obs[row], explore=e, action_mask=m)
+                                     for e in (True, True, True, False)]
+            r["sample_calls"].append(algo.sample_calls)
+        res[f"compute-{name}"] = r
+        algo.stop()
+    # the server's fallback (hidden 128: outside rlks_policy_act's scope)
+    for name, attrs in (("plain", {}), ("masked", {"action_mask": "room"})):
+        algo = decide_algo(torch, jtab, jspec, H=128, **attrs)
+        srv = algo.server(max_rows=300)
+        assert not srv.fused
+        obs = np.random.default_rng(6).random((300, algo.D)).astype(np.float32)
+        r = {"calls": [srv.calls]}
+        for n in (300, 1):
+            for mk in ((True,) if attrs else (False, True)):
+                m = decide_masks(algo.A, n, 4) if mk else None
+                for k, explore in enumerate((True, True, False)):
+                    acts, info = srv.act(obs[:n], explore=explore, action_mask=m, full_fetch=True)
+                    r[f"n{n}-mask{int(mk)}-call{k}"] = sha(acts) + "".join(sha(info[key])[:16] for key in sorted(info))
+                    r["calls"].append(srv.calls)
+        one, info = srv.act(obs[0], explore=True, action_mask=decide_masks(algo.A, 2, 4)[1], full_fetch=True)
+        r["single"] = [one, info["action_logp"], info["vf_preds"], sha(info["action_dist_inputs"]), sha(info["action_prob"])]
+        res[f"server-{name}"] = r
+        srv.close()
+        algo.stop()
+    # evaluate
+    params2 = PolicyParams(6, 256, 2, device=dev, seed=3)
+    r = {}
+    for pol in ("round_robin", "greedy", "cheapest", "myopic", "random", params2):
+        e = evaluate(pol, 5, seed=42, device=dev)
+        r[pol if isinstance(pol, str) else "params"] = {"rewards": sha(e.rewards), "actions": sha(e.actions), "names": list(e.names)}
+    res["evaluate"] = r
+    # evaluate_nodes / evaluate_lanes on the fill-up spec
+    masked_algo = decide_algo(torch, jtab, jspec, action_mask="room")
+    params3 = policy(torch, 9, 256, 3, "WIDE")  # 3 actions: the generic-width forward
+    kw = dict(nodes=jspec, table=jtab, seed=11, device=dev)
+    r, lanes = {}, {}
+    for name, pol in (("myopic_with_room", "myopic_with_room"), ("least_loaded", "least_loaded"), ("params", params3),
+                      ("masked-ppo", masked_algo)):
+        e = evaluate_nodes(pol, 5, **kw)
+        r[name] = {"rewards": sha(e.rewards), "actions": sha(e.actions), "choices": e.choices.tolist(),
+                   "counts": [e.placed, e.rejected, e.departed], "mean_util": sha(e.mean_util), "extra": e.extra}
+        if not isinstance(pol, str):
+            for flag in (None, True, False):
+                lanes[f"{name}-mask-{flag}"] = sha(evaluate_lanes(pol, 5, action_mask=flag, **kw))
+                r[f"{name}-mask-{flag}"] = sha(evaluate_nodes(pol, 5, action_mask=flag, **kw).actions)
+    assert r["masked-ppo-mask-True"] != r["masked-ppo-mask-False"], "the mask does not bite"
+    res["evaluate_nodes"], res["evaluate_lanes"] = r, lanes
+    # PPO.evaluate() with baselines
+    table_algo = decide_algo(torch, load_table(), evaluation_baselines=["round_robin", "cheapest", "myopic"],
+                             evaluation_duration=5)
+    masked_algo.config.evaluation_baselines, masked_algo.config.evaluation_duration = ["myopic", "least_loaded"], 5
+    res["ppo_evaluate"] = {"table": json.dumps(table_algo.evaluate(), sort_keys=True),
+                           "node": json.dumps(masked_algo.evaluate(), sort_keys=True),
+                           "node-unmasked": json.dumps(masked_algo.evaluate(action_mask=False), sort_keys=True)}
+    # DecisionLog.collect and estimate() with the target given each way
+    r, est = {}, {}
+    # (4 clusters: a server built from a checkpoint forwards through the fused kernels, which take 2, 4 or 8
+    # actions; nodes of one pod, so that clusters fill within the 6 steps)
+    spec4 = rr.node_spec(dataclasses.replace(case, C=4, cpu=(100,) * 4, mem=(4096,) * 4))
+    algo4 = decide_algo(torch, synthetic_table(4, 100, seed=7), spec4, action_mask="room")
+    for name, algo, lanes_, nodes in (("table", table_algo, 4, None), ("node-masked", algo4, 8, spec4)):
+        log = DecisionLog.collect(algo, 6, lanes=lanes_, table=algo.table, nodes=nodes, seed=9)
+        r[name] = {k: sha(v) for k, v in log.to_numpy().items()}
+        greedy = DecisionLog.collect(algo.params, 6, lanes=lanes_, table=algo.table, nodes=nodes, seed=9, explore=False)
+        r[name + "-params-greedy"] = {k: sha(v) for k, v in greedy.to_numpy().items()}
+        other = decide_algo(torch, algo.table, nodes, **({"action_mask": "room"} if nodes is not None else {}))
+        other.params.flat.mul_(1.5)  # a target that is not the behaviour policy
+        srv = other.server()
+        for way, target in (("ppo", other), ("params", other.params), ("server", srv),
+                            ("checkpoint", other.save(str(tmp / f"ckpt-{name}")))):
+            lp = target_logp(target, log)
+            rec, _ = run_estimate(lp, torch.as_tensor(log.logp, device=dev), torch.as_tensor(log.rewards, device=dev),
+                                  torch.as_tensor(log.dones, device=dev), 0.99)
+            est[f"{name}-{way}"] = {"logp": sha(lp), "record": sha(rec), "estimate": json.dumps(estimate(target, log),
+                                                                                              sort_keys=True)}
+        srv.close()
+        other.stop()
+    res["collect"], res["estimate"] = r, est
+    for a in (masked_algo, table_algo, algo4):
+        a.stop()
+    return res
+
+
 def compact(res):
     """the result as JSON with one line per case (an entry of a section), so that the file stays short"""
     secs = []
@@ -289,11 +435,21 @@ def compact(res):
     return "{\n" + ",\n".join(secs) + "\n}\n"
 
 
-def run(out):
+def run(out, only=None):
+    import tempfile
+
     import torch
     from rlks import _lib
 
-    res = {"lib": os.environ.get("RLKS_LIB_NAME", "tree"), "rollout": {}, "grad": {}, "sgd": {}}
+    res = {"lib": os.environ.get("RLKS_LIB_NAME", "tree")}
+    with tempfile.TemporaryDirectory() as tmp:
+        res["decide"] = decide_digest(torch, Path(tmp))
+    print("decide", {k: len(v) for k, v in res["decide"].items()}, flush=True)
+    if only == "decide":
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(compact(res))
+        return
+    res.update(rollout={}, grad={}, sgd={})
     res["ws"] = ws_digest(torch)
     print("ws", {k: v["bytes"] for k, v in res["ws"].items()}, flush=True)
     res["gather"] = gather_digest(torch)
@@ -371,5 +527,7 @@ def compare(pa, pb):
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         compare(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "--decide":
+        run(Path(sys.argv[2]), only="decide")
     else:
         run(Path(sys.argv[1]))
