@@ -317,6 +317,20 @@ int rlks_absmax(const float* x, int rows, int cols, int ld, uint32_t* slot, void
 int rlks_rollout_ws(rlks_env* env, const rlks_mlp_desc* desc, const float* params_dev,
                     const rlks_rollout_bufs* bufs, int explore, void* workspace, int64_t ws_bytes,
                     void* stream);
+/* The form (RLKS_ROLLOUT_*) rlks_rollout_ws runs for this env, policy and buffers: a host query, nothing is
+ * launched.  The rollout entries decide with the same function, so the answer is what they run.  rlks_rollout
+ * runs the fp32 kernels for every desc of the fused widths, whatever its precision: its form is the one this
+ * query names for the same desc with RLKS_PRECISION_FP32.  A table
+ * env's fused forms are taken only while their LDS (own buffers + both tables) fits a workgroup's 160 KiB;
+ * that part of the choice depends on the kernels the entry runs, n_actions, the table's size and the env's autoreset
+ * flag alone, so the ranks of one job resolve alike.  The per-step forms need autoreset lanes: without
+ * them an over-budget shape is RLKS_ERR_UNSUPPORTED, the message naming the bytes asked and the limit. */
+int rlks_rollout_form(rlks_env* env, const rlks_mlp_desc* desc, const rlks_rollout_bufs* bufs, int32_t* form);
+/* LDS bytes per workgroup of the fused rollout kernel of `form` (RLKS_ROLLOUT_SF16_PERSISTENT,
+ * RLKS_ROLLOUT_FP32_FUSED_32 / _128) with a table env of n_rows x n_clouds: its launcher's dynamic bytes plus
+ * the static bytes hipFuncGetAttributes reports. */
+int rlks_rollout_lds_bytes(const rlks_mlp_desc* desc, int32_t form, int32_t n_rows, int32_t n_clouds,
+                           int64_t* bytes);
 
 /* Minibatch rows per packed record: [obs D | logits_old A | adv | vtarg | logp_old | action] */
 int rlks_minibatch_stride(const rlks_mlp_desc* desc);

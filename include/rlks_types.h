@@ -111,6 +111,19 @@ enum {
                               reference's fp32, a secondary figure only; rollouts as RLKS_PRECISION_SF16 */
 };
 
+/* The form a rollout runs in (rlks_rollout_form).  A table env's rollout kernels stage the
+ * env's two tables in LDS beside their own buffers; a form that would ask for more than a workgroup's
+ * 160 KiB is passed over for the next one.  The per-step forms hold the tables alone. */
+enum {
+  RLKS_ROLLOUT_SF16_PERSISTENT = 0, /* k_sf_roll: the whole rollout in one launch */
+  RLKS_ROLLOUT_SF16_PER_STEP = 1,   /* per step k_sf_fwd16, then rlks_env_sample_step */
+  RLKS_ROLLOUT_FP32_FUSED_32 = 2,   /* per step k_fwd_head<..., FWD_ROLLOUT> on 32-row tiles; values in one pass */
+  RLKS_ROLLOUT_FP32_FUSED_128 = 3,  /* the same on 128-row tiles (more than 32,768 lanes) */
+  RLKS_ROLLOUT_FP32_PER_STEP = 4,   /* per step the fp32 policy forward, then rlks_env_sample_step */
+  RLKS_ROLLOUT_WIDE = 5,            /* generic-width path (wide_mlp.hip) */
+  RLKS_ROLLOUT_NODE = 6             /* node-level env: forward of both nets, then the sampling node step */
+};
+
 /* One split-fp16 GEMM (fp32 in / fp32 out, fp32-accurate): C = epi(op(A) op(B)), op = transpose
  * when trans_*; operand scales come from max|x| slots (uint bits of a non-negative float). */
 enum {

@@ -52,6 +52,9 @@ namespace rlks {
 
 constexpr int ENV_BLOCK = 256;
 constexpr int MAX_TABLE_BYTES = 128 * 1024;  // LDS budget for the staged tables (gfx950: 160 KB per workgroup)
+// LDS a workgroup can be given on gfx950.  The env kernels hold the tables alone; a fused rollout kernel
+// holds them beside its own buffers, so its form is chosen against this limit (rollout.hip rollout_form)
+constexpr int MAX_LDS_BYTES = 160 * 1024;
 
 struct EnvView {
   int N, T, C, max_steps, noise_mode, autoreset, env_offset, track_returns;

@@ -287,6 +287,13 @@ struct Dh1Args {
 // host launchers (mlp_fwd.hip / mlp_bwd.hip)
 enum { FWD_ONLY = 0, FWD_TRAIN = 1, FWD_ROLLOUT = 2 };
 int launch_fwd_head(const FwdArgs& a, int net, int A, int mode, hipStream_t s);
+// forward-only and rollout launches of up to this many rows run 32-row tiles, larger ones 128-row tiles
+constexpr int FWD_SMALL_MAX_ROWS = 32 * 1024;
+// the fused fp32 rollout step (k_fwd_head<..., FWD_ROLLOUT>: policy forward, draw, env step) on 32- or
+// 128-row tiles, and the LDS bytes that launch asks for with a table env of table_rows x clouds: the
+// launcher's own dynamic count plus the kernel's static bytes (hipFuncGetAttributes)
+int launch_fwd_rollout(const FwdArgs& a, int A, int tile_rows, hipStream_t s);
+int fwd_rollout_lds(int A, int tile_rows, int table_rows, int clouds, int64_t* bytes);
 int launch_dw2(const Dw2Args& a, int D, int splits, hipStream_t s);
 int launch_dh1(const Dh1Args& a, int D, hipStream_t s);
 

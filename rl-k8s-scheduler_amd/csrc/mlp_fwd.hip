@@ -12,6 +12,8 @@
 //   dZ2 = (dout W3) * (1 - H2^2) -> HBM (the only activation that leaves the chip), and per-tile
 //   partial sums of db2 = colsum dZ2, dW3 = dout^T H2, db3, loss stats (fixed-order reduction
 //   later, so the gradient is bit-reproducible run to run).
+#include <utility>
+
 #include "mlp_common.h"
 
 namespace rlks {
@@ -323,19 +325,42 @@ static int launch_cfg(const FwdArgs& a, hipStream_t s) {
   return RLKS_OK;
 }
 
+// the kernel's static LDS as the runtime reports it (the compiler drops sVx where no path reads it)
+template <int A_, int WM, int WN, int DD>
+static int fwd_rollout_static(int64_t* bytes) {
+  static const std::pair<hipError_t, int64_t> st = [] {  // asked once
+    hipFuncAttributes fa{};
+    const hipError_t e =
+        hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_fwd_head<A_, 0, WM, WN, FWD_ROLLOUT, DD>));
+    return std::make_pair(e, (int64_t)fa.sharedSizeBytes);
+  }();
+  RLKS_HIP(st.first);
+  *bytes = st.second;
+  return RLKS_OK;
+}
+
+template <int A_, int DD>
+static int fwd_rollout_lds_a(int tile_rows, int table_doubles, int64_t* bytes) {
+  int64_t st = 0;
+  if (int rc = tile_rows == 128 ? fwd_rollout_static<A_, 4, 2, DD>(&st) : fwd_rollout_static<A_, 1, 4, DD>(&st)) return rc;
+  *bytes = st + (int64_t)(tile_rows == 128 ? fwd_lds_bytes<4, 2>(A_, DD, table_doubles)
+                                           : fwd_lds_bytes<1, 4>(A_, DD, table_doubles));
+  return RLKS_OK;
+}
+
 template <int A_, int NET, int DD>
 static int launch_net(const FwdArgs& a, int mode, hipStream_t s) {
   if (mode == FWD_TRAIN) return launch_cfg<A_, NET, 4, 2, FWD_TRAIN, DD>(a, s);
+  if (mode == FWD_ROLLOUT) return fail(RLKS_ERR_ARG, "the fused rollout step is launched by launch_fwd_rollout");
   // small batches (rollouts of a few thousand lanes) use 32-row tiles with the 4 waves split
   // over columns so that more CUs get work; large batches use 128-row tiles
-  const bool small = a.M <= 32 * 1024;
-  if (mode == FWD_ROLLOUT) {
-    if constexpr (NET == 0) {
-      return small ? launch_cfg<A_, 0, 1, 4, FWD_ROLLOUT, DD>(a, s) : launch_cfg<A_, 0, 4, 2, FWD_ROLLOUT, DD>(a, s);
-    }
-    return fail(RLKS_ERR_ARG, "rollout mode drives the policy net");
-  }
+  const bool small = a.M <= FWD_SMALL_MAX_ROWS;
   return small ? launch_cfg<A_, NET, 1, 4, FWD_ONLY, DD>(a, s) : launch_cfg<A_, NET, 4, 2, FWD_ONLY, DD>(a, s);
+}
+
+template <int A_, int DD>
+static int launch_rollout_a(const FwdArgs& a, int tile_rows, hipStream_t s) {
+  return tile_rows == 128 ? launch_cfg<A_, 0, 4, 2, FWD_ROLLOUT, DD>(a, s) : launch_cfg<A_, 0, 1, 4, FWD_ROLLOUT, DD>(a, s);
 }
 
 // obs_dim = 3 x clusters (cost, latency, utilisation per cluster): C = 2, 4, 8 -> D = 6, 12, 24
@@ -345,6 +370,28 @@ int launch_fwd_head(const FwdArgs& a, int net, int A, int mode, hipStream_t s) {
     case 2: return net ? launch_net<1, 1, 6>(a, mode, s) : launch_net<2, 0, 6>(a, mode, s);
     case 4: return net ? launch_net<1, 1, 12>(a, mode, s) : launch_net<4, 0, 12>(a, mode, s);
     case 8: return net ? launch_net<1, 1, 24>(a, mode, s) : launch_net<8, 0, 24>(a, mode, s);
+    default: return fail(RLKS_ERR_UNSUPPORTED, "fused policy head is built for 2, 4 or 8 actions");
+  }
+}
+
+int launch_fwd_rollout(const FwdArgs& a, int A, int tile_rows, hipStream_t s) {
+  if (a.D != 3 * A) return fail(RLKS_ERR_UNSUPPORTED, "fused MLP kernels expect obs_dim = 3 x n_actions");
+  RLKS_REQUIRE(tile_rows == 32 || tile_rows == 128, RLKS_ERR_ARG, "fused rollout step: 32- or 128-row tiles");
+  switch (A) {
+    case 2: return launch_rollout_a<2, 6>(a, tile_rows, s);
+    case 4: return launch_rollout_a<4, 12>(a, tile_rows, s);
+    case 8: return launch_rollout_a<8, 24>(a, tile_rows, s);
+    default: return fail(RLKS_ERR_UNSUPPORTED, "fused policy head is built for 2, 4 or 8 actions");
+  }
+}
+
+int fwd_rollout_lds(int A, int tile_rows, int table_rows, int clouds, int64_t* bytes) {
+  RLKS_REQUIRE(tile_rows == 32 || tile_rows == 128, RLKS_ERR_ARG, "fused rollout step: 32- or 128-row tiles");
+  const int td = 2 * table_rows * clouds;  // launch_cfg's count: both tables, doubles
+  switch (A) {
+    case 2: return fwd_rollout_lds_a<2, 6>(tile_rows, td, bytes);
+    case 4: return fwd_rollout_lds_a<4, 12>(tile_rows, td, bytes);
+    case 8: return fwd_rollout_lds_a<8, 24>(tile_rows, td, bytes);
     default: return fail(RLKS_ERR_UNSUPPORTED, "fused policy head is built for 2, 4 or 8 actions");
   }
 }

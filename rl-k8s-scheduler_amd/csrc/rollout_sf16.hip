@@ -1,7 +1,7 @@
 // rollout_sf16.hip — one rollout step of the c2 hot path on split-fp16 MFMA: both nets' forward
 // (pi logits and vf values of the step's observations), TorchCategorical sampling (Philox) and the
 // env step, in one launch per step.  With the values computed here, the rollout needs no separate
-// value pass (only V(obs[T]) for the bootstrap, FWD_ONLY mode).
+// value pass: step T of the persistent kernel is the bootstrap V(obs[T]).
 //
 // Reference: the env step is K8sMultiCloudEnv.step (k8s_multi_cloud_env.py:115-144) via
 // env_device.h:step_lane; the policy is RLlib's FCNet [256, 256] tanh with a separate value net
@@ -18,6 +18,8 @@
 //            steps the env lanes.
 // The latency of one step is what matters at c2 (4,096 lanes = 128 workgroups); the split products
 // are fp32-accurate as in sgd_sf16.hip.
+#include <utility>
+
 #include "sgd_sf16.h"
 
 namespace rlks {
@@ -50,7 +52,7 @@ __device__ __forceinline__ float tanh_abs(float x) {
 // diagnostic build only (tools/stamps.py --roll): [workgroup][wave 0 / wave 4][phase] clocks of step 0
 __device__ unsigned long long g_roll_stamps[256][2][8];
 #define RL_STAMP(i) \
-  if (t == 0 && (w == 0 || w == 4) && l == 0 && blockIdx.x < 256 && MODE == FWD_ROLLOUT) \
+  if (t == 0 && (w == 0 || w == 4) && l == 0 && blockIdx.x < 256) \
   g_roll_stamps[blockIdx.x][w >> 2][i] = __builtin_amdgcn_s_memtime()
 #else
 #define RL_STAMP(i)
@@ -59,9 +61,11 @@ __device__ unsigned long long g_roll_stamps[256][2][8];
 // FWD_ROLLOUT: the whole rollout in one launch.  A workgroup's 32 env lanes depend on nothing
 // outside the workgroup, so it loops over the T steps itself: weights, tables and W1a fragments are
 // staged once, each step's observations stay in LDS for the next step (and go to HBM for the
-// update), and step T is the bootstrap value pass.  FWD_ONLY: one forward of M rows.
+// update), and step T is the bootstrap value pass.  MODE stays in the signature (the kernels' names);
+// FWD_ROLLOUT is its only value.
 template <int A_, int KD, int MODE>
 __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
+  static_assert(MODE == FWD_ROLLOUT, "k_sf_roll is the persistent rollout");
   constexpr int KS = KD / 16;
   constexpr float H1S = 16384.f;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
   const int m = row0 + r;
   const bool valid = m < M;
   const SfRollNet& N = g.n[net];
-  const int steps = MODE == FWD_ROLLOUT ? g.T : 0;
+  const int steps = g.T;
 
   // ---- once: b2 / W3 of both nets and the tables in LDS; this wave's W1a fragments in registers
   for (int e = tid; e < 2 * (1 + A_) * HID; e += 512) {
@@ -88,11 +92,10 @@ __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
     const int An_ = nn == 0 ? A_ : 1;
     sBW[e] = rem < HID ? Q.b2[rem] : (rem - HID < An_ * HID ? Q.w3[rem - HID] : 0.f);
   }
-  if (MODE == FWD_ROLLOUT)
-    for (int e = tid; e < g.env.T * g.env.C; e += 512) {
-      sTab[e] = g.tab_cost[e];
-      sTab[g.env.T * g.env.C + e] = g.tab_lat[e];
-    }
+  for (int e = tid; e < g.env.T * g.env.C; e += 512) {
+    sTab[e] = g.tab_cost[e];
+    sTab[g.env.T * g.env.C + e] = g.tab_lat[e];
+  }
   for (int e = tid; e < 32 * KD; e += 512) {  // observations of step 0: Xa = [X | 1 | 0]
     const int rr = e / KD, d = e - rr * KD;
     sObs[e] = (row0 + rr < M && d < D) ? g.x[(size_t)(row0 + rr) * D + d] : (d == D ? 1.f : 0.f);
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
                                  (sPart[((4 + 2) * A_) * 32 + r] + sPart[((4 + 3) * A_) * 32 + r]));
       g.values[tN + m] = v;
     }
-    if (w == 0 && h == 0 && valid && (MODE == FWD_ONLY || t < steps)) {
+    if (w == 0 && h == 0 && valid && t < steps) {
       float lg[A_];
 #pragma unroll
       for (int a = 0; a < A_; ++a)
@@ -242,22 +245,20 @@ __global__ __launch_bounds__(512) void k_sf_roll(SfRollArgs g) {
       if (g.logits)
 #pragma unroll
         for (int a = 0; a < A_; ++a) g.logits[(tN + m) * A_ + a] = lg[a];
-      if (MODE == FWD_ROLLOUT) {
-        // TorchCategorical: sample (Philox, counter = lane / episode / step) or argmax (explore = 0)
-        const EnvView& v = g.env;
-        float lp;
-        const int act = categorical_row<A_>(lg, g.explore != 0, action_ctr(v, m, v.episode[m], v.step[m]), v.k0, v.k1,
-                                            lp);
-        g.actions[tN + m] = act;
-        g.logp[tN + m] = lp;
-        // next observation straight into this lane's LDS row, then to obs[t + 1] in HBM
-        float* o = sObs + r * KD;
-        const StepOut so = step_lane(v, sTab, m, act, o, nullptr);
-        float* og = g.x + ((size_t)(t + 1) * M + m) * D;
-        for (int d = 0; d < D; ++d) og[d] = o[d];
-        g.rewards[tN + m] = (float)so.reward;
-        g.dones[tN + m] = (uint8_t)so.done;
-      }
+      // TorchCategorical: sample (Philox, counter = lane / episode / step) or argmax (explore = 0)
+      const EnvView& v = g.env;
+      float lp;
+      const int act = categorical_row<A_>(lg, g.explore != 0, action_ctr(v, m, v.episode[m], v.step[m]), v.k0, v.k1,
+                                          lp);
+      g.actions[tN + m] = act;
+      g.logp[tN + m] = lp;
+      // next observation straight into this lane's LDS row, then to obs[t + 1] in HBM
+      float* o = sObs + r * KD;
+      const StepOut so = step_lane(v, sTab, m, act, o, nullptr);
+      float* og = g.x + ((size_t)(t + 1) * M + m) * D;
+      for (int d = 0; d < D; ++d) og[d] = o[d];
+      g.rewards[tN + m] = (float)so.reward;
+      g.dones[tN + m] = (uint8_t)so.done;
     }
     RL_STAMP(5);
     __syncthreads();  // sObs of step t + 1 complete; sH / sPart free
@@ -270,24 +271,50 @@ extern "C" int rlks_dbg_roll_stamps(unsigned long long* host) {
 }
 #endif
 
+// dynamic LDS of k_sf_roll<A_, KD>: sH, sPart, sBW, sObs, then both tables
 template <int A_, int KD>
-static int launch_roll_a(const SfRollArgs& a, int mode, hipStream_t s) {
-  const size_t lds = (size_t)2 * 8 * 2 * 2 * 64 * 16 + (size_t)2 * 4 * A_ * 32 * sizeof(float) +
-                     (size_t)2 * (1 + A_) * HID * sizeof(float) + (size_t)32 * KD * sizeof(float) +
-                     (mode == FWD_ROLLOUT ? (size_t)2 * a.env.T * a.env.C * sizeof(double) : 0);
-  const dim3 grid(cdiv(a.M, 32));
-  if (mode == FWD_ROLLOUT) hipLaunchKernelGGL((k_sf_roll<A_, KD, FWD_ROLLOUT>), grid, dim3(512), lds, s, a);
-  else hipLaunchKernelGGL((k_sf_roll<A_, KD, FWD_ONLY>), grid, dim3(512), lds, s, a);
+static size_t roll_lds_bytes(int table_rows, int clouds) {
+  return (size_t)2 * 8 * 2 * 2 * 64 * 16 + (size_t)2 * 4 * A_ * 32 * sizeof(float) +
+         (size_t)2 * (1 + A_) * HID * sizeof(float) + (size_t)32 * KD * sizeof(float) +
+         (size_t)2 * table_rows * clouds * sizeof(double);
+}
+
+template <int A_, int KD>
+static int launch_roll_a(const SfRollArgs& a, hipStream_t s) {
+  const size_t lds = roll_lds_bytes<A_, KD>(a.env.T, a.env.C);
+  hipLaunchKernelGGL((k_sf_roll<A_, KD, FWD_ROLLOUT>), dim3(cdiv(a.M, 32)), dim3(512), lds, s, a);
   RLKS_LAUNCHED();
   return RLKS_OK;
 }
 
-int launch_sf_roll(const SfRollArgs& a, int mode, hipStream_t s) {
+template <int A_, int KD>
+static int roll_lds_a(int table_rows, int clouds, int64_t* bytes) {
+  // the kernel's static LDS as the runtime reports it, asked once
+  static const std::pair<hipError_t, int64_t> st = [] {
+    hipFuncAttributes fa{};
+    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_sf_roll<A_, KD, FWD_ROLLOUT>));
+    return std::make_pair(e, (int64_t)fa.sharedSizeBytes);
+  }();
+  RLKS_HIP(st.first);
+  *bytes = st.second + (int64_t)roll_lds_bytes<A_, KD>(table_rows, clouds);
+  return RLKS_OK;
+}
+
+int launch_sf_roll(const SfRollArgs& a, hipStream_t s) {
   RLKS_REQUIRE(a.D == 3 * a.A, RLKS_ERR_UNSUPPORTED, "split-fp16 rollout expects obs_dim = 3 x n_actions");
   switch (a.A) {
-    case 2: return launch_roll_a<2, 16>(a, mode, s);
-    case 4: return launch_roll_a<4, 16>(a, mode, s);
-    case 8: return launch_roll_a<8, 32>(a, mode, s);
+    case 2: return launch_roll_a<2, 16>(a, s);
+    case 4: return launch_roll_a<4, 16>(a, s);
+    case 8: return launch_roll_a<8, 32>(a, s);
+    default: return fail(RLKS_ERR_UNSUPPORTED, "split-fp16 rollout is built for 2, 4 or 8 actions");
+  }
+}
+
+int sf_roll_lds(int A, int table_rows, int clouds, int64_t* bytes) {
+  switch (A) {
+    case 2: return roll_lds_a<2, 16>(table_rows, clouds, bytes);
+    case 4: return roll_lds_a<4, 16>(table_rows, clouds, bytes);
+    case 8: return roll_lds_a<8, 32>(table_rows, clouds, bytes);
     default: return fail(RLKS_ERR_UNSUPPORTED, "split-fp16 rollout is built for 2, 4 or 8 actions");
   }
 }

@@ -82,11 +82,11 @@ struct SfRollNet {
 };
 struct SfRollArgs {
   SfRollNet n[2];
-  float* x;        // FWD_ONLY: [M][D] observations; FWD_ROLLOUT: obs [T+1][M][D] (obs[0] read)
-  int M, D, A, T;  // T: rollout steps (FWD_ROLLOUT); buffers below are time-major [T(+1)][M]
-  float* logits;   // [(T)][M][A] or null
-  float* values;   // [(T+1)][M] or null
-  // FWD_ROLLOUT: sample, step the env lane m = row m
+  float* x;        // obs [T+1][M][D] (obs[0] read)
+  int M, D, A, T;  // T: rollout steps; buffers below are time-major [T(+1)][M]
+  float* logits;   // [T][M][A] or null
+  float* values;   // [T+1][M] or null
+  // sample, step the env lane m = row m
   EnvView env;
   const double* tab_cost;
   const double* tab_lat;
@@ -97,7 +97,10 @@ struct SfRollArgs {
   float* rewards;
   uint8_t* dones;
 };
-int launch_sf_roll(const SfRollArgs& a, int mode, hipStream_t s);
+int launch_sf_roll(const SfRollArgs& a, hipStream_t s);
+// the LDS bytes that launch asks for with a table env of table_rows x clouds: the launcher's own dynamic
+// count plus the kernel's static bytes (hipFuncGetAttributes)
+int sf_roll_lds(int A, int table_rows, int clouds, int64_t* bytes);
 
 // forward of both nets on 16-row tiles (sgd_sf16.hip k_sf_fwd16): out[0] = logits [M][A] (or null:
 // the value net alone), out[1] = values [M] (or null)

@@ -26,6 +26,9 @@ RLKS_PRECISION_FP32, RLKS_PRECISION_SF16, RLKS_PRECISION_WIDE, RLKS_PRECISION_F1
 RLKS_STAT_POLICY_LOSS, RLKS_STAT_VF_LOSS, RLKS_STAT_KL, RLKS_STAT_ENTROPY, RLKS_STAT_ROWS = 0, 1, 2, 3, 4
 RLKS_STAT_GRAD_GNORM = 5
 RLKS_EPLOG_CAP = 128
+# the form a rollout runs in (include/rlks_types.h RLKS_ROLLOUT_*, rlks_rollout_form)
+(RLKS_ROLLOUT_SF16_PERSISTENT, RLKS_ROLLOUT_SF16_PER_STEP, RLKS_ROLLOUT_FP32_FUSED_32, RLKS_ROLLOUT_FP32_FUSED_128,
+ RLKS_ROLLOUT_FP32_PER_STEP, RLKS_ROLLOUT_WIDE, RLKS_ROLLOUT_NODE) = range(7)
 # rlks_rollout_metrics record slots (include/rlks_types.h RLKS_RM_*)
 (RLKS_RM_ROWS, RLKS_RM_REWARD_SUM, RLKS_RM_REWARD_MIN, RLKS_RM_REWARD_MAX, RLKS_RM_DONES, RLKS_RM_VALUE_SUM,
  RLKS_RM_VTARG_SUM, RLKS_RM_VTARG_SQ, RLKS_RM_RESID_SUM, RLKS_RM_RESID_SQ, RLKS_RM_FIXED) = range(11)
@@ -148,6 +151,8 @@ SIGNATURES = {
     "rlks_absmax": [_P, _I, _I, _I, _P, _P],
     "rlks_policy_forward_ws": [C.POINTER(MlpDesc), _P, _P, _I, _P, _P, _P, _I64, _P],
     "rlks_rollout_ws": [_P, C.POINTER(MlpDesc), _P, C.POINTER(RolloutBufs), _I, _P, _I64, _P],
+    "rlks_rollout_form": [_P, C.POINTER(MlpDesc), C.POINTER(RolloutBufs), C.POINTER(C.c_int32)],
+    "rlks_rollout_lds_bytes": [C.POINTER(MlpDesc), C.c_int32, C.c_int32, C.c_int32, C.POINTER(_I64)],
     "rlks_minibatch_stride": [C.POINTER(MlpDesc)],
     "rlks_ppo_gather": [C.POINTER(MlpDesc), C.POINTER(RolloutBufs), C.c_uint64, _I, _I64, _I, _P, _P, _P],
     "rlks_ppo_gather_grouped": [C.POINTER(MlpDesc), C.POINTER(RolloutBufs), C.c_uint64, _I, _I, _I, _I64, _I, _P,
@@ -201,7 +206,8 @@ class RlksError(RuntimeError):
 _lib = None
 # entry points an older variant library (RLKS_LIB, same-box A/B runs) may lack: diagnostics and build
 # introspection, never compute.  The product library must export all of them (tests/test_abi_host.py)
-_OPTIONAL = {n for n in SIGNATURES if n.startswith("rlks_debug_")} | {"rlks_sf_f1_fused"}
+_OPTIONAL = {n for n in SIGNATURES if n.startswith("rlks_debug_")} | {"rlks_sf_f1_fused", "rlks_rollout_form",
+                                                                       "rlks_rollout_lds_bytes"}
 
 
 def _warn_if_stale() -> None:

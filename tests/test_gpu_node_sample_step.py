@@ -220,8 +220,9 @@ def _row(C, nodes, H, N, T, mb, rows=100, prec="auto", per_step=False, explore=T
 @pytest.mark.parametrize("C,nodes,H,N,T,mb,rows,prec,per_step,explore", [
     _row(8, 16, 256, 520, 16, 8192, id="8-16-256-520-16-8192"),   # split-fp16, node_rollout
     _row(16, 32, 384, 136, 8, 1024, id="16-32-384-136-8-1024"),   # hidden 384: wide_rollout
-    # table envs (nodes=None): every kernel that draws inside a rollout.  96 lanes leave the last 32-row
-    # tile ragged; a 4-row table ends every episode after 3 steps, so the counter's episode word moves
+    # table envs (nodes=None): every kernel that draws inside a rollout.  96 lanes are three full 32-row
+    # tiles (test_gpu_table_rollout.py runs the ragged one); a 4-row table ends every episode after 3 steps,
+    # so the counter's episode word moves
     _row(2, None, 256, 96, 6, 256, rows=4, id="table-persistent-2"),             # k_sf_roll
     _row(8, None, 256, 96, 6, 256, rows=4, id="table-persistent-8"),
     _row(2, None, 256, 96, 6, 256, rows=4, explore=False, id="table-persistent-2-argmax"),

@@ -49,6 +49,7 @@ ROLLOUTS = {  # name: C, nodes, H, N, T, minibatch, table rows, sgd_precision, p
     "table-persistent-8": (8, None, 256, 96, 6, 256, 4, "auto", False),
     "table-per-step-4": (4, None, 256, 96, 6, 256, 4, "auto", True),
     "table-fp32-4": (4, None, 256, 96, 6, 256, 4, "fp32", False),
+    "table-fp32-128-2": (2, None, 256, 32776, 2, 128, 100, "fp32", False),  # past 32,768 lanes: 128-row tiles
     "table-wide-4": (4, None, 384, 136, 6, 256, 4, "auto", False),
     "table-filtered-4": (4, None, 256, 96, 6, 256, 4, "auto", False, {"observation_filter": "MeanStdFilter"}),
     "node-masked-8": (8, 16, 256, 520, 16, 8192, 100, "auto", False, {"action_mask": "room"}),
